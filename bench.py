@@ -7,13 +7,22 @@ Workload: 3-D 7-point Poisson, npts = 1025 (1023^3 unknowns, the reference's ver
 Jacobi smoother with scale 6/7, RHS f = -3 pi^2 sin sin sin, u0 = 0.  A "step" is one V-cycle
 (src/solver.c:1531-1549), including its residual-norm reduction.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1: launched by torch.distributed.run, one rank per GPU; the grid is z-slab decomposed
   (strong scaling: the total problem is fixed), halos travel over RCCL (C side, include/mg_comm.h).
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (fine-level Jacobi sweep, HIP-event timed
-inside the timed region) and "cpu_baseline" (the CPU oracle's assembled-CSR V-cycle on a bounded
-sample, timed on this box's host cores).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(`ms_per_step` is one timed step) with what the same timed region yields besides: "roofline" (the
+fine-level launches, HIP-event timed inside the timed region) and "cycle_roofline".
+--dump-outputs DIR: after the timed steps, the arrays a caller of the timed path receives, as .npy
+(float64): residual_norms.npy (the solver's residual history, every cycle so far) and
+solution_sample.npy (u at a fixed, seeded sample of at most 2^22 unknowns; with N > 1 each rank
+writes solution_sample_rank<r>.npy from its slab, the sample split among the ranks).
+--full adds what takes work of its own: the residual histories against tests/golden/bench_history.json,
+the plain one-sweep kernel and the measured STREAM ceiling ("roofline.plain_sweep",
+"roofline.measured_ceiling"), the other single-GPU BASELINE configurations ("configs") and the CPU
+baselines ("cpu_baseline": the CPU oracle's assembled-CSR V-cycle on a bounded sample, and the
+reference's own loop on the host cores for config 2).
 """
 import argparse
 import ctypes as C
@@ -53,18 +62,18 @@ def cpu_baseline(args):
 
 
 def cpu_reference_loop(threads, npts=2049):
-    """the reference's OWN V-cycle loop (src/solver.c:1526-1553, unmodified objects of /root/reference/src/*.c) on the
+    """the reference's OWN V-cycle loop (src/solver.c:1526-1553, unmodified objects of the reference's src/*.c) on the
     host cores, over a PETSc-equivalent CPU data path -- assembled CSR SpMV + Jacobi + BLAS-1 (MGPETSC_NO_RECOGNITION=1: the matrices
     the reference assembles are applied as matrices) -- timed by the reference's own `Solver walltime` window.  The binary
-    (build/refdriver/poisson_cpu, made by __graft_entry__.build() where the reference tree exists) links the drop-in's host logic with
+    (oracle/_ref/poisson_cpu, made by __graft_entry__.build() where the reference tree exists) links the drop-in's host logic with
     a host-memory OpenMP backend of the kernel ABI; it is a bench-only artefact, PETSc itself being unavailable offline: kind "port".
     2-D, the family of BASELINE config 2, at a bounded npts."""
     import re
     import subprocess
     import tempfile
-    exe = os.path.join(ROOT, "build", "refdriver", "poisson_cpu")
+    exe = os.path.join(ROOT, "oracle", "_ref", "poisson_cpu")
     if not os.path.exists(exe):
-        return {"value": None, "error": "build/refdriver/poisson_cpu is not built (it needs the reference tree at build time)"}
+        return {"value": None, "error": "oracle/_ref/poisson_cpu is not built (it needs the reference tree at build time)"}
     levels = 0
     while (npts - 1) % (2 ** levels) == 0 and (npts - 1) // (2 ** levels) - 1 >= 1:
         levels += 1
@@ -278,6 +287,25 @@ def run_config(dim, npts, precision, steps, warmup, device):
     return out
 
 
+DUMP_SAMPLE = 1 << 22       # unknowns of u written by --dump-outputs (32 MiB of float64 in all)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(s, d, rank, world):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the residual history (rank 0; every rank holds the
+    same all-reduced one) and u, at a fixed seeded sample of this rank's unknowns when there are more than the budget"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    if rank == 0:
+        np.save(os.path.join(d, "residual_norms.npy"), np.asarray(s.rnorm, dtype=np.float64))
+    u = s.solution()
+    k = DUMP_SAMPLE // world
+    if u.size > k:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).integers(0, u.size, size=k))
+        u = u[idx]
+    np.save(os.path.join(d, "solution_sample.npy" if world == 1 else f"solution_sample_rank{rank}.npy"), np.asarray(u, dtype=np.float64))
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a CHILD job (`python -m torch.distributed.run`, one rank per
     GPU, rendezvous on 127.0.0.1) and relay its output and exit code.  This process has not touched HIP (nothing imported so far
@@ -314,12 +342,16 @@ def main():
     ap.add_argument("--dim", type=int, default=3)
     ap.add_argument("--precision", choices=["fp64", "mixed"], default="fp64",
                     help="mixed = BASELINE config 5: fp32 smoother sweeps, fp64 residual/correction (1 GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configurations (2-D 4097^2, 3-D 513^3, mixed 1025^3)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the other BASELINE configurations (2-D 4097^2, 3-D 513^3, mixed 1025^3)")
     ap.add_argument("--cpu-npts", type=int, default=257)
     ap.add_argument("--cpu-levels", type=int, default=8)
     ap.add_argument("--cpu-cycles", type=int, default=120)
     ap.add_argument("--cpu-threads", type=int, default=16)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the golden residual histories, the kernel probes, the other BASELINE configurations and the CPU baselines")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -454,6 +486,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
+    if args.dump_outputs:
+        dump_outputs(s, args.dump_outputs, rank, world)
 
     dof_per_cycle = s.dof_updates_per_cycle
     value = dof_per_cycle * args.steps / elapsed
@@ -530,46 +564,48 @@ def main():
                                      "bytes_per_fine_unknown": cb / float(n0) ** args.dim,
                                      "model": "bytes one cycle of THIS implementation must move (fused passes; DESIGN.md section 4)",
                                      "survey_8d3": survey_cycle_bytes(args.dim, float(n0) ** args.dim, elapsed / args.steps)}
-            out["history"] = check_history(f"{args.dim}d_{args.npts}_{args.precision}", rn)
+            if args.full:
+                out["history"] = check_history(f"{args.dim}d_{args.npts}_{args.precision}", rn)
     s.close()
     failures = []
     if rank == 0:
-        if world == 1 and pair_n and args.dim == 3 and args.precision == "fp64":
-            try:     # the plain one-sweep kernel beside it (north_star: >= 70 % of 8 TB/s on the fp64 smoother sweep)
-                ps = plain_sweep_probe(local_rank, n0)
-                ps["traffic"] = tj.get("jacobi_sweep_hbm_bytes_per_launch") if args.npts == 1025 else None
-                out["roofline"]["plain_sweep"] = ps
-                achieved = ps["achieved"]
-            except Exception as e:   # reporting only
-                out["roofline"]["plain_sweep"] = {"error": str(e)}
-        if world == 1 and achieved:
-            try:
-                tri = stream_ceiling(local_rank, local_unknowns)
-                tri["sweep_over_triad"] = achieved / tri["GB/s"]
-                out["roofline"]["measured_ceiling"] = tri
-            except Exception as e:   # reporting only
-                out["roofline"]["measured_ceiling"] = {"error": str(e)}
-        default_headline = (world == 1 and args.dim == 3 and args.npts == 1025 and args.precision == "fp64")
-        if default_headline and not args.no_configs:
-            # the other single-GPU BASELINE configurations ride in the same line (configs 2, 3, 5); config 4 is the N > 1 run
-            out["configs"] = []
-            for name, (d_, np_, pr_) in (("config2", (2, 4097, "fp64")), ("config3", (3, 513, "fp64")), ("config5", (3, 1025, "mixed"))):
-                try:
-                    c_ = run_config(d_, np_, pr_, 10, 2, local_rank)
+        if args.full:
+            if world == 1 and pair_n and args.dim == 3 and args.precision == "fp64":
+                try:     # the plain one-sweep kernel beside it (north_star: >= 70 % of 8 TB/s on the fp64 smoother sweep)
+                    ps = plain_sweep_probe(local_rank, n0)
+                    ps["traffic"] = tj.get("jacobi_sweep_hbm_bytes_per_launch") if args.npts == 1025 else None
+                    out["roofline"]["plain_sweep"] = ps
+                    achieved = ps["achieved"]
                 except Exception as e:   # reporting only
-                    c_ = {"error": str(e)}
-                c_["baseline_config"] = name
-                if name == "config2" and not args.no_cpu_baseline:
-                    try:     # the CPU column of the one configuration the reference itself can run (reporting only)
-                        c_["cpu_baseline"] = cpu_reference_loop(args.cpu_threads)
-                    except Exception as e:   # noqa: BLE001
-                        c_["cpu_baseline"] = {"value": None, "error": str(e)}
-                out["configs"].append(c_)
-        if not args.no_cpu_baseline and world == 1:
-            try:
-                out["cpu_baseline"] = cpu_baseline(args)
-            except Exception as e:   # the baseline is reporting only; never fail the GPU line for it
-                out["cpu_baseline"] = {"value": None, "error": str(e)}
+                    out["roofline"]["plain_sweep"] = {"error": str(e)}
+            if world == 1 and achieved:
+                try:
+                    tri = stream_ceiling(local_rank, local_unknowns)
+                    tri["sweep_over_triad"] = achieved / tri["GB/s"]
+                    out["roofline"]["measured_ceiling"] = tri
+                except Exception as e:   # reporting only
+                    out["roofline"]["measured_ceiling"] = {"error": str(e)}
+            default_headline = (world == 1 and args.dim == 3 and args.npts == 1025 and args.precision == "fp64")
+            if default_headline and not args.no_configs:
+                # the other single-GPU BASELINE configurations ride in the same line (configs 2, 3, 5); config 4 is the N > 1 run
+                out["configs"] = []
+                for name, (d_, np_, pr_) in (("config2", (2, 4097, "fp64")), ("config3", (3, 513, "fp64")), ("config5", (3, 1025, "mixed"))):
+                    try:
+                        c_ = run_config(d_, np_, pr_, 10, 2, local_rank)
+                    except Exception as e:   # reporting only
+                        c_ = {"error": str(e)}
+                    c_["baseline_config"] = name
+                    if name == "config2" and not args.no_cpu_baseline:
+                        try:     # the CPU column of the one configuration the reference itself can run (reporting only)
+                            c_["cpu_baseline"] = cpu_reference_loop(args.cpu_threads)
+                        except Exception as e:   # noqa: BLE001
+                            c_["cpu_baseline"] = {"value": None, "error": str(e)}
+                    out["configs"].append(c_)
+            if not args.no_cpu_baseline and world == 1:
+                try:
+                    out["cpu_baseline"] = cpu_baseline(args)
+                except Exception as e:   # the baseline is reporting only; never fail the GPU line for it
+                    out["cpu_baseline"] = {"value": None, "error": str(e)}
         print(json.dumps(out), flush=True)
         # the line is printed whatever happened; a configuration that crashed or a residual history that left the committed one makes
         # the run FAIL (exit 5) -- only the cpu_baseline leg is reporting-only

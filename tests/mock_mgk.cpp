@@ -955,7 +955,7 @@ int mgk_error_sums_f64(mgk_ctx *c, const mgk_geom *g, const double *u, const dou
     e3[0] = m; e3[1] = s1; e3[2] = s2;
     return 0;
 }
-// (the _Pragma lines: no-ops in the test builds; bench.py's CPU baseline artefact build/refdriver/poisson_cpu is this file compiled -O3 -fopenmp --
+// (the _Pragma lines: no-ops in the test builds; bench.py's CPU baseline artefact oracle/_ref/poisson_cpu is this file compiled -O3 -fopenmp --
 // the CSR / BLAS-1 data path of the reference's PETSc on the host cores)
 #define FLAT(NAME, ARGS, BODY) int NAME ARGS { if (!c) return fail(MGK_EINVAL, #NAME); return run(c, [=] { _Pragma("omp parallel for schedule(static)") for (long q = 0; q < n; q++) { BODY; } }); }
 FLAT(mgk_flat_axpy, (mgk_ctx *c, long n, double a, const double *x, double *y, void *), y[q] = y[q] + a * x[q])

@@ -16,7 +16,8 @@ from oracle import Oracle
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "multigrid_petsc_amd", "csrc")
 OUT = os.path.join(ROOT, "tests", "_san")
-REF = "/root/reference"
+REF_O1 = os.path.join(ROOT, "oracle", "_ref", "o1")     # the reference's own driver objects (oracle/Makefile `ref`, made by __graft_entry__.build())
+REF_SRC = ("array", "matbuild", "mesh", "problem", "solver", "poisson")
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]
 ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=99", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
 
@@ -45,12 +46,8 @@ def san():
     _cc(["gcc", "-std=c99", "-D_POSIX_C_SOURCE=200809L"] + SAN + inc + [os.path.join(CSRC, "driver", "mgpoisson.c")] + objs + ["-o", exes["mgpoisson"]] + link)
     exes["slab"] = os.path.join(OUT, "san_slab")
     _cc(["gcc", "-std=c99", "-D_POSIX_C_SOURCE=200809L"] + SAN + inc + [os.path.join(ROOT, "tests", "san_slab.c")] + objs + ["-o", exes["slab"]] + link)
-    if os.path.isdir(os.path.join(REF, "src")):
-        robjs = []
-        for f in ("array", "matbuild", "mesh", "problem", "solver", "poisson"):
-            o = os.path.join(OUT, "ref_" + f + ".o")      # the reference's own sources, compiled where they lie, NOT sanitized (their
-            _cc(["gcc", "-std=c99", "-O1", "-w", "-I" + os.path.join(REF, "include")] + inc + ["-c", os.path.join(REF, "src", f + ".c"), "-o", o])   # leaks are theirs)
-            robjs.append(o)
+    robjs = [os.path.join(REF_O1, f + ".o") for f in REF_SRC]      # the reference's own sources at -O1, NOT sanitized (their leaks are theirs)
+    if all(os.path.exists(o) for o in robjs):
         exes["refdriver"] = os.path.join(OUT, "san_refdriver")
         _cc(["gcc"] + robjs + objs + ["-o", exes["refdriver"]] + link)
     return exes
@@ -202,7 +199,7 @@ REF_LEAKS = "leak:MultigridVcycle\nleak:MultigridPetscPCMG\nleak:MultigridIcycle
 
 def _refdrv(san, tmp_path, opts, env=None):
     if "refdriver" not in san:
-        pytest.skip("the reference tree is not on this machine")
+        pytest.skip("oracle/_ref/o1 is not built (no reference tree at build time)")
     (tmp_path / "poisson.in").write_text(opts)
     (tmp_path / "lsan.supp").write_text(REF_LEAKS)
     e = dict(env or {})

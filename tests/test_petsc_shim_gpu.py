@@ -4,7 +4,7 @@
    the shim's own entry points (MatCreateAIJ/MatSetValue/.../KSPSolve/KSPBuildResidual/MatMult/VecAXPY/VecNorm),
    with stencil recognition on (matrix-free kernels) and off (generic AIJ kernel): both must reproduce the oracle.
 2. reference-driver leg: the reference's UNMODIFIED src/*.c, linked against the drop-in by __graft_entry__.build()
-   (build/refdriver/poisson), run on the GPU with an options file of ours; its outputs (rData.dat, uData.dat,
+   (oracle/_ref/poisson), run on the GPU with an options file of ours; its outputs (rData.dat, uData.dat,
    eData.dat, iteration count) are compared with the oracle."""
 import ctypes as C
 import os
@@ -18,7 +18,7 @@ from oracle import Oracle
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFDRV = os.path.join(ROOT, "build", "refdriver", "poisson")
+REFDRV = os.path.join(ROOT, "oracle", "_ref", "poisson")
 ADD, INSERT, FINAL, NORM_2 = 2, 1, 0, 1
 
 
@@ -198,8 +198,8 @@ def _run_reference_driver(tmp_path, opts, extra_env=None):
     return it, rdat, u, e, out
 
 
-@pytest.mark.skipif(not os.path.exists(REFDRV), reason="build/refdriver/poisson absent: __graft_entry__.build() links it only "
-                    "where /root/reference exists (the build container); the binary then travels with the snapshot")
+@pytest.mark.skipif(not os.path.exists(REFDRV), reason="oracle/_ref/poisson absent: __graft_entry__.build() links it only "
+                    "where the reference tree exists; the binary then travels with the tree")
 @pytest.mark.parametrize("npts,levels,scale,env", [
     (17, 2, 0.8, None), (17, 2, 1.0, None), (129, 7, 0.8, None), (129, 6, 0.8, None), (513, 9, 0.8, None),
     (33, 4, 0.8, {"MGPETSC_NO_RECOGNITION": "1"}),
@@ -220,7 +220,7 @@ def test_unmodified_reference_driver_on_the_gpu(orc, tmp_path, npts, levels, sca
     assert "matrix-free 5-point stencil" in out or env  # KSPView reports the recognised operator
 
 
-@pytest.mark.skipif(not os.path.exists(REFDRV), reason="build/refdriver/poisson absent")
+@pytest.mark.skipif(not os.path.exists(REFDRV), reason="oracle/_ref/poisson absent")
 @pytest.mark.parametrize("npts,levels,v0,v1,mesh", [
     (33, 4, 1, 1, 0), (65, 5, 2, 4, 0), (129, 7, 4, 1, 0), (257, 8, 4, 4, 0), (513, 9, 5, 2, 0), (257, 5, 3, 3, 0), (129, 6, 2, 2, 2), (257, 8, 4, 3, 1),
 ])
@@ -235,7 +235,7 @@ def test_reference_driver_sweep_counts_and_depths_on_the_gpu(orc, tmp_path, npts
     assert np.array_equal(u, ref["u"])
 
 
-@pytest.mark.skipif(not os.path.exists(REFDRV), reason="build/refdriver/poisson absent")
+@pytest.mark.skipif(not os.path.exists(REFDRV), reason="oracle/_ref/poisson absent")
 def test_reference_driver_default_options_file(orc, tmp_path):
     """the reference's default run (poisson.in: npts 17, 2 grids, 2 levels, V(3,3), no -pc_type): PETSc would use ILU(0);
     the drop-in says so on stderr and smooths with Jacobi, scale 1 -> 99 cycles."""
@@ -265,7 +265,7 @@ def test_own_driver_names_the_mapping_style_it_was_given(tmp_path):
         assert line.split(":")[1].strip() == name
 
 
-@pytest.mark.skipif(not os.path.exists(REFDRV), reason="build/refdriver/poisson absent")
+@pytest.mark.skipif(not os.path.exists(REFDRV), reason="oracle/_ref/poisson absent")
 @pytest.mark.parametrize("mesh,npts,levels,env", [(1, 33, 4, None), (2, 33, 4, None), (1, 129, 6, None), (2, 65, 5, None), (1, 513, 8, None),
                                                   (1, 65, 5, {"MGPETSC_NO_RECOGNITION": "1"})])
 def test_reference_driver_stretched_meshes(orc, tmp_path, mesh, npts, levels, env):
@@ -286,7 +286,7 @@ def test_reference_driver_stretched_meshes(orc, tmp_path, mesh, npts, levels, en
     assert ("assembled AIJ (generic CSR kernel)" if env else "row-dependent coefficients") in out
 
 
-@pytest.mark.skipif(not os.path.exists(REFDRV), reason="build/refdriver/poisson absent")
+@pytest.mark.skipif(not os.path.exists(REFDRV), reason="oracle/_ref/poisson absent")
 @pytest.mark.parametrize("mesh,npts,levels", [(0, 65, 5), (0, 257, 7), (1, 65, 5), (2, 129, 6), (1, 513, 8)])
 def test_reference_driver_chebyshev_on_stretched_meshes(orc, tmp_path, mesh, npts, levels):
     """KSPCHEBYSHEV + PCJACOBI through the unmodified reference driver over the drop-in: on the constant stencil (-mesh 0) and on
@@ -306,7 +306,7 @@ def test_reference_driver_chebyshev_on_stretched_meshes(orc, tmp_path, mesh, npt
 MGPOISSON = os.path.join(ROOT, "multigrid_petsc_amd", "mgpoisson")
 
 
-@pytest.mark.skipif(not os.path.exists(REFDRV), reason="build/refdriver/poisson absent")
+@pytest.mark.skipif(not os.path.exists(REFDRV), reason="oracle/_ref/poisson absent")
 @pytest.mark.parametrize("npts,levels,mesh", [(17, 2, 0), (65, 5, 0), (129, 7, 0), (65, 5, 1), (129, 6, 2)])
 def test_own_driver_writes_the_reference_output_files(tmp_path, npts, levels, mesh):
     """the product's own driver against the reference's own Postprocessing code (unmodified
@@ -338,7 +338,7 @@ def test_own_driver_writes_the_reference_output_files(tmp_path, npts, levels, me
     assert info(out_ref) == info(p.stdout)
 
 
-@pytest.mark.skipif(not os.path.exists(REFDRV), reason="build/refdriver/poisson absent")
+@pytest.mark.skipif(not os.path.exists(REFDRV), reason="oracle/_ref/poisson absent")
 @pytest.mark.parametrize("npts,levels,scale,ksp", [(17, 2, 1.0, "richardson"), (33, 5, 0.8, "richardson"), (129, 7, 0.8, "richardson"),
                                                    (513, 9, 0.8, "richardson"), (65, 5, None, "chebyshev")])
 def test_reference_driver_cycle8_pcmg(orc, tmp_path, npts, levels, scale, ksp):
@@ -407,7 +407,7 @@ def _pcmg_exact_coarse(orc, _dense, npts, levels, sweeps, scale, maxiter, rtol=1
     return np.array(hist), x
 
 
-@pytest.mark.skipif(not os.path.exists(REFDRV), reason="build/refdriver/poisson absent")
+@pytest.mark.skipif(not os.path.exists(REFDRV), reason="oracle/_ref/poisson absent")
 @pytest.mark.parametrize("npts,levels,coarse", [(33, 3, "default"), (33, 2, "default"), (65, 3, "lu"), (65, 5, "default"), (129, 3, "lu")])
 def test_reference_driver_cycle8_exact_coarse_solve(orc, tmp_path, npts, levels, coarse):
     """-cycle 8 with PETSc's default coarse solver (preonly + LU, src/solver.c:1931-1932 takes it as it comes): the drop-in inverts
@@ -427,7 +427,7 @@ def test_reference_driver_cycle8_exact_coarse_solve(orc, tmp_path, npts, levels,
     assert "type: lu" in out and "type: preonly" in out
 
 
-@pytest.mark.skipif(not os.path.exists(REFDRV), reason="build/refdriver/poisson absent")
+@pytest.mark.skipif(not os.path.exists(REFDRV), reason="oracle/_ref/poisson absent")
 @pytest.mark.parametrize("npts,scale,env", [(9, 0.8, None), (17, 1.0, None), (33, 0.8, None), (17, 0.8, {"MGPETSC_NO_RECOGNITION": "1"})])
 def test_reference_driver_cycle1_single_grid(orc, tmp_path, npts, scale, env):
     """-cycle 1 (MultigridIcycle, src/solver.c:1991-2060) with one grid: a monitored Richardson +
@@ -477,7 +477,7 @@ def _level_operator(orc, npts, grids):
     return np.block(blocks), np.concatenate(b), n
 
 
-@pytest.mark.skipif(not os.path.exists(REFDRV), reason="build/refdriver/poisson absent")
+@pytest.mark.skipif(not os.path.exists(REFDRV), reason="oracle/_ref/poisson absent")
 @pytest.mark.parametrize("npts,grids,iters,env", [(9, 2, 25, None), (17, 2, 25, None), (65, 2, 25, None), (17, 2, 25, {"MGPETSC_NO_RECOGNITION": "1"}),
                                                   (65, 2, 25, {"MGPETSC_NO_RECOGNITION": "1"}), (17, 3, 25, None), (33, 3, 20, None), (33, 4, 20, None),
                                                   (65, 3, 20, None), (33, 4, 20, {"MGPETSC_NO_RECOGNITION": "1"})])

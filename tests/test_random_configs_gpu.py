@@ -30,7 +30,7 @@ def test_random_slab_configurations_equal_the_oracle():
 
 
 @pytest.mark.timeout(600)
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "build", "refdriver", "poisson")), reason="build/refdriver/poisson absent (linked where /root/reference exists)")
+@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "poisson")), reason="oracle/_ref/poisson absent (linked where the reference tree exists)")
 def test_random_reference_driver_options_equal_the_oracle():
     """the reference's unmodified driver over the drop-in: size, depth, -v, -mesh, -map, damping and the drop-in's fast-path switches drawn at random"""
     _run("stress_refdriver.py", 30, 21, 500)

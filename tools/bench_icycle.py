@@ -1,7 +1,7 @@
 """-cycle 1 with several grids in one level (the I-cycle's coupled operator, src/solver.c:255-487) through the reference's UNMODIFIED
 driver over the drop-in: seconds per Richardson iteration (sweep + residual + norm) with the block operator recognised (stencil /
 transfer kernels on [fine | coarse] vectors) and with recognition off (assembled AIJ on the generic CSR kernel).
-Usage: python tools/bench_icycle.py [npts] [iters] [grids]   (needs build/refdriver/poisson from __graft_entry__.build())"""
+Usage: python tools/bench_icycle.py [npts] [iters] [grids]   (needs oracle/_ref/poisson from __graft_entry__.build())"""
 import os
 import re
 import subprocess
@@ -19,7 +19,7 @@ for tag, env in (("recognised", {}), ("generic CSR", {"MGPETSC_NO_RECOGNITION": 
         open(os.path.join(d, "poisson.in"), "w").write(opts)
         e = dict(os.environ)
         e.update(env)
-        p = subprocess.run([os.path.join(ROOT, "build", "refdriver", "poisson")], cwd=d, env=e, stdout=subprocess.PIPE,
+        p = subprocess.run([os.path.join(ROOT, "oracle", "_ref", "poisson")], cwd=d, env=e, stdout=subprocess.PIPE,
                            stderr=subprocess.STDOUT, text=True, timeout=900)
         out = p.stdout
         wall = [float(x) for x in re.findall(r"Solver walltime:\s+([0-9.eE+-]+)", out)]

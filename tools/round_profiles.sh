@@ -20,7 +20,7 @@ pmc() {     # name, counter, script...
     rm -rf $O/raw_$name
 }
 cd $R
-stats bench_1023 python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-configs
+stats bench_1023 python3 $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-configs
 echo "bench_1023 done"
 pmc pmc_fetch_size_3d FETCH_SIZE python3 $R/tools/pmc_sweep.py
 pmc pmc_write_size_3d WRITE_SIZE python3 $R/tools/pmc_sweep.py
@@ -33,6 +33,6 @@ stats config3_513 python3 $R/tools/trace_config.py 3 513
 echo "configs done"
 python3 $R/tools/pmc_traffic.py $O/pmc_fetch_size_3d.csv $O/pmc_write_size_3d.csv 1070599167 > $O/traffic_3d.json
 python3 $R/tools/pmc_traffic.py $O/pmc_fetch_size_2d.csv $O/pmc_write_size_2d.csv 16769025 > $O/traffic_2d.json
-python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20_stderr.txt
+python3 $R/bench.py --steps 20 --warmup 5 --full > $O/bench_steps20.json 2> $O/bench_steps20_stderr.txt
 echo "bench rc=$?"
 ls $O
