@@ -71,6 +71,8 @@ def _sigs(L):
         "mgk_set_tuning": (None, [i, i]),
         "mgk_geom_init_f32": (i, [G, i, i, i, i]),
         "mgk_jacobi_f32": (i, [vp, G, c_dp, d, d, vp, vp, vp, vp]),
+        "mgk_jacobi_range_f32": (i, [vp, G, c_dp, d, d, vp, vp, vp, i, i, vp]),
+        "mgk_jacobi2_slab_f32": (i, [vp, G, G, c_dp, d, d, vp, vp, vp, vp, i, i, i, i, vp]),
         "mgk_jacobi_zero_f32": (i, [vp, G, d, d, vp, vp, vp]),
         "mgk_residual_f32": (i, [vp, G, c_dp, vp, vp, vp, vp]),
         "mgk_restrict_fw_f32": (i, [vp, G, G, vp, vp, vp]),

@@ -158,6 +158,13 @@ void mgo_st_jacobi_f32(int n, const float *As, float dinv, float scale, const fl
 void mgo_st_residual_f32(int n, const float *As, const float *b, const float *u, float *r);
 void mgo_st_restrict_f32(int nf, const float *rf, float *bc);
 void mgo_st_prolong_add_f32(int nf, const float *uc, float *uf);
+/* the same on nx x ny x nz grids (Dirichlet at z = -1 and z = nz; restriction: coarse ((nxf-1)/2) x ((nyf-1)/2) x nzc); the cube
+ * forms above are these with nx = ny = nz = n */
+void mgo_st_jacobi_f32_thin(int nx, int ny, int nz, const float *As, float dinv, float scale, const float *b, const float *u,
+                            float *unew, int zero_guess);
+void mgo_st_residual_f32_thin(int nx, int ny, int nz, const float *As, const float *b, const float *u, float *r);
+void mgo_st_restrict_f32_thin(int nxf, int nyf, int nzf, int nzc, const float *rf, float *bc);
+void mgo_st_prolong_add_f32_thin(int nxf, int nyf, int nzf, int nzc, const float *uc, float *uf);
 int  mgo_vcycle_mixed(const mgo_vcycle_cfg *cfg, double *rnorm_raw, double *u_out, double *bnorm_out, double *solve_seconds);
 
 #ifdef __cplusplus

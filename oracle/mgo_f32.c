@@ -16,89 +16,114 @@
 #include <string.h>
 #include <time.h>
 
-static inline float st_row32(int n, const float *As, const float *x, int k, int i, int j) {
-    long nn = (long)n * n, c = ((long)k * n + i) * n + j;
+/* Thin forms: nx x ny x nz grids (compact index (k*ny+i)*nx+j), homogeneous Dirichlet on every face (z = -1 and z = nz included),
+ * as the fp64 mgo_st_*(dim, n, nz, ...) forms.  The cube entry points below call them with nx = ny = nz = n: same loops, same
+ * arithmetic, same bits. */
+static inline float st_row32(int nx, int ny, int nz, const float *As, const float *x, int k, int i, int j) {
+    long nn = (long)nx * ny, c = ((long)k * ny + i) * nx + j;
     float sum = 0.0f;
     if (k - 1 >= 0) sum += As[0] * x[c - nn];
-    if (i - 1 >= 0) sum += As[1] * x[c - n];
+    if (i - 1 >= 0) sum += As[1] * x[c - nx];
     if (j - 1 >= 0) sum += As[2] * x[c - 1];
     sum += As[3] * x[c];
-    if (j + 1 < n) sum += As[4] * x[c + 1];
-    if (i + 1 < n) sum += As[5] * x[c + n];
-    if (k + 1 < n) sum += As[6] * x[c + nn];
+    if (j + 1 < nx) sum += As[4] * x[c + 1];
+    if (i + 1 < ny) sum += As[5] * x[c + nx];
+    if (k + 1 < nz) sum += As[6] * x[c + nn];
     return sum;
 }
 
-void mgo_st_jacobi_f32(int n, const float *As, float dinv, float scale, const float *b, const float *u,
-                       float *unew, int zero_guess) {
-#pragma omp parallel for collapse(2) schedule(static) if ((long)n * n * n > 32768)
-    for (int k = 0; k < n; k++)
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < n; j++) {
-                long c = ((long)k * n + i) * n + j;
+void mgo_st_jacobi_f32_thin(int nx, int ny, int nz, const float *As, float dinv, float scale, const float *b, const float *u,
+                            float *unew, int zero_guess) {
+#pragma omp parallel for collapse(2) schedule(static) if ((long)nx * ny * nz > 32768)
+    for (int k = 0; k < nz; k++)
+        for (int i = 0; i < ny; i++)
+            for (int j = 0; j < nx; j++) {
+                long c = ((long)k * ny + i) * nx + j;
                 if (zero_guess) { float z = b[c] * dinv; unew[c] = scale * z; continue; }
-                float t = st_row32(n, As, u, k, i, j);
+                float t = st_row32(nx, ny, nz, As, u, k, i, j);
                 float r = b[c] - t;
                 float z = r * dinv;
                 unew[c] = u[c] + scale * z;
             }
 }
 
-void mgo_st_residual_f32(int n, const float *As, const float *b, const float *u, float *r) {
-#pragma omp parallel for collapse(2) schedule(static) if ((long)n * n * n > 32768)
-    for (int k = 0; k < n; k++)
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < n; j++) {
-                long c = ((long)k * n + i) * n + j;
-                r[c] = b[c] - st_row32(n, As, u, k, i, j);
+void mgo_st_residual_f32_thin(int nx, int ny, int nz, const float *As, const float *b, const float *u, float *r) {
+#pragma omp parallel for collapse(2) schedule(static) if ((long)nx * ny * nz > 32768)
+    for (int k = 0; k < nz; k++)
+        for (int i = 0; i < ny; i++)
+            for (int j = 0; j < nx; j++) {
+                long c = ((long)k * ny + i) * nx + j;
+                r[c] = b[c] - st_row32(nx, ny, nz, As, u, k, i, j);
             }
 }
 
-void mgo_st_restrict_f32(int nf, const float *rf, float *bc) {
-    int nc = (nf - 1) / 2;
-    long nnf = (long)nf * nf;
+/* fine nxf x nyf x nzf -> coarse nxc x nyc x nzc, nxc = (nxf-1)/2, nyc = (nyf-1)/2; coarse plane kc gathers the fine planes
+ * 2 kc + {0,1,2}; a fine plane beyond nzf - 1 has no matrix entry (mgo_st_restrict without fzhi) */
+void mgo_st_restrict_f32_thin(int nxf, int nyf, int nzf, int nzc, const float *rf, float *bc) {
+    int nxc = (nxf - 1) / 2, nyc = (nyf - 1) / 2;
+    long nnf = (long)nxf * nyf;
     static const float w2[9] = {0.0625f, 0.125f, 0.0625f, 0.125f, 0.25f, 0.125f, 0.0625f, 0.125f, 0.0625f};
     static const float w1[3] = {0.25f, 0.5f, 0.25f};
-#pragma omp parallel for collapse(2) schedule(static) if ((long)nc * nc * nc > 32768)
-    for (int k1 = 0; k1 < nc; k1++)
-        for (int i1 = 0; i1 < nc; i1++)
-            for (int j1 = 0; j1 < nc; j1++) {
+#pragma omp parallel for collapse(2) schedule(static) if ((long)nxc * nyc * nzc > 32768)
+    for (int k1 = 0; k1 < nzc; k1++)
+        for (int i1 = 0; i1 < nyc; i1++)
+            for (int j1 = 0; j1 < nxc; j1++) {
                 float sum = 0.0f;
-                for (int dk = 0; dk < 3; dk++)
+                for (int dk = 0; dk < 3; dk++) {
+                    if (2 * k1 + dk >= nzf) continue;
                     for (int di = 0; di < 3; di++)
                         for (int dj = 0; dj < 3; dj++)
-                            sum += (w1[dk] * w2[di * 3 + dj]) * rf[(2 * k1 + dk) * nnf + (long)(2 * i1 + di) * nf + 2 * j1 + dj];
-                bc[((long)k1 * nc + i1) * nc + j1] = sum;
+                            sum += (w1[dk] * w2[di * 3 + dj]) * rf[(2 * k1 + dk) * nnf + (long)(2 * i1 + di) * nxf + 2 * j1 + dj];
+                }
+                bc[((long)k1 * nyc + i1) * nxc + j1] = sum;
             }
 }
 
-void mgo_st_prolong_add_f32(int nf, const float *uc, float *uf) {
-    int nc = (nf - 1) / 2;
-    long ncc = (long)nc * nc;
-#pragma omp parallel for collapse(2) schedule(static) if ((long)nf * nf * nf > 32768)
-    for (int k = 0; k < nf; k++)
-        for (int i = 0; i < nf; i++)
-            for (int j = 0; j < nf; j++) {
+/* uf += P uc, fine nxf x nyf x nzf, coarse ((nxf-1)/2) x ((nyf-1)/2) x nzc; coarse planes outside [0, nzc) are zero */
+void mgo_st_prolong_add_f32_thin(int nxf, int nyf, int nzf, int nzc, const float *uc, float *uf) {
+    int nxc = (nxf - 1) / 2, nyc = (nyf - 1) / 2;
+    long ncc = (long)nxc * nyc;
+#pragma omp parallel for collapse(2) schedule(static) if ((long)nxf * nyf * nzf > 32768)
+    for (int k = 0; k < nzf; k++)
+        for (int i = 0; i < nyf; i++)
+            for (int j = 0; j < nxf; j++) {
                 int kc0 = (k & 1) ? (k - 1) / 2 : k / 2 - 1, kc1 = (k & 1) ? kc0 : k / 2;
                 int ic0 = (i & 1) ? (i - 1) / 2 : i / 2 - 1, ic1 = (i & 1) ? ic0 : i / 2;
                 int jc0 = (j & 1) ? (j - 1) / 2 : j / 2 - 1, jc1 = (j & 1) ? jc0 : j / 2;
                 float sum = 0.0f;
                 for (int kc = kc0; kc <= kc1; kc++) {
-                    if (kc < 0 || kc >= nc) continue;
+                    if (kc < 0 || kc >= nzc) continue;
                     float wk = (k & 1) ? 1.0f : 0.5f;
                     for (int ic = ic0; ic <= ic1; ic++) {
-                        if (ic < 0 || ic >= nc) continue;
+                        if (ic < 0 || ic >= nyc) continue;
                         float wi = (i & 1) ? 1.0f : 0.5f;
                         for (int jc = jc0; jc <= jc1; jc++) {
-                            if (jc < 0 || jc >= nc) continue;
+                            if (jc < 0 || jc >= nxc) continue;
                             float wj = (j & 1) ? 1.0f : 0.5f;
-                            sum += (wk * (wi * wj)) * uc[kc * ncc + (long)ic * nc + jc];
+                            sum += (wk * (wi * wj)) * uc[kc * ncc + (long)ic * nxc + jc];
                         }
                     }
                 }
-                long c = ((long)k * nf + i) * nf + j;
+                long c = ((long)k * nyf + i) * nxf + j;
                 uf[c] = uf[c] + sum;
             }
+}
+
+void mgo_st_jacobi_f32(int n, const float *As, float dinv, float scale, const float *b, const float *u,
+                       float *unew, int zero_guess) {
+    mgo_st_jacobi_f32_thin(n, n, n, As, dinv, scale, b, u, unew, zero_guess);
+}
+
+void mgo_st_residual_f32(int n, const float *As, const float *b, const float *u, float *r) {
+    mgo_st_residual_f32_thin(n, n, n, As, b, u, r);
+}
+
+void mgo_st_restrict_f32(int nf, const float *rf, float *bc) {
+    mgo_st_restrict_f32_thin(nf, nf, nf, (nf - 1) / 2, rf, bc);
+}
+
+void mgo_st_prolong_add_f32(int nf, const float *uc, float *uf) {
+    mgo_st_prolong_add_f32_thin(nf, nf, nf, (nf - 1) / 2, uc, uf);
 }
 
 typedef struct { int n; long N; float As[7], dinv; float *u, *b, *rv, *tmp; } l32;

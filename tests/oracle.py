@@ -78,6 +78,10 @@ class Oracle:
         L.mgo_st_residual_f32.argtypes = [C.c_int] + [C.c_void_p] * 4
         L.mgo_st_restrict_f32.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         L.mgo_st_prolong_add_f32.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        L.mgo_st_jacobi_f32_thin.argtypes = [C.c_int] * 3 + [C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 3 + [C.c_int]
+        L.mgo_st_residual_f32_thin.argtypes = [C.c_int] * 3 + [C.c_void_p] * 4
+        L.mgo_st_restrict_f32_thin.argtypes = [C.c_int] * 4 + [C.c_void_p] * 2
+        L.mgo_st_prolong_add_f32_thin.argtypes = [C.c_int] * 4 + [C.c_void_p] * 2
         L.mgo_pcmg.restype = C.c_int
         L.mgo_pcmg.argtypes = [C.POINTER(VcycleCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.mgo_icycle.restype = C.c_int
@@ -190,28 +194,64 @@ class Oracle:
         return {"iters": it, "rnorm": rn[:it + 1].copy(), "u": u, "bnorm": bn.value}
 
     # ---- fp32 leg ----
-    def jacobi32(self, n, As, scale, b, u, zero_guess=False):
-        As32 = np.asarray(As, dtype=np.float32)
-        dinv = np.float32(1.0 / As[3])
-        out = np.zeros(n ** 3, dtype=np.float32)
-        self.L.mgo_st_jacobi_f32(n, _p(As32), dinv, np.float32(scale), _p(b), _p(u), _p(out), int(zero_guess))
+    # n: unknowns per row; ny (default n) rows per plane; nz (default n) planes.  nz = None and ny = None call the cube entry points,
+    # anything else the thin forms (mgo_st_*_f32_thin).  Inputs must be contiguous float32 arrays of the grid's size.
+    @staticmethod
+    def _f32(a, size):
+        a = np.ascontiguousarray(a)
+        if a.dtype != np.float32 or a.size != size:
+            raise ValueError(f"fp32 oracle: need {size} float32 values, got {a.size} {a.dtype}")
+        return a
+
+    @staticmethod
+    def coef32(As):
+        """the operator as the fp32 leg evaluates it: (float) As[q], (float) (1 / As[3])"""
+        return np.asarray(As, dtype=np.float32), np.float32(1.0 / As[3])
+
+    def jacobi32(self, n, As, scale, b, u, zero_guess=False, nz=None, ny=None):
+        nyv, nzv = (n if ny is None else ny), (n if nz is None else nz)
+        N = n * nyv * nzv
+        As32, dinv = self.coef32(As)
+        b, u = self._f32(b, N), self._f32(u, N)
+        out = np.zeros(N, dtype=np.float32)
+        if ny is None and nz is None:
+            self.L.mgo_st_jacobi_f32(n, _p(As32), dinv, np.float32(scale), _p(b), _p(u), _p(out), int(zero_guess))
+        else:
+            self.L.mgo_st_jacobi_f32_thin(n, nyv, nzv, _p(As32), dinv, np.float32(scale), _p(b), _p(u), _p(out), int(zero_guess))
         return out
 
-    def residual32(self, n, As, b, u):
-        As32 = np.asarray(As, dtype=np.float32)
-        out = np.zeros(n ** 3, dtype=np.float32)
-        self.L.mgo_st_residual_f32(n, _p(As32), _p(b), _p(u), _p(out))
+    def residual32(self, n, As, b, u, nz=None, ny=None):
+        nyv, nzv = (n if ny is None else ny), (n if nz is None else nz)
+        N = n * nyv * nzv
+        As32 = self.coef32(As)[0]
+        b, u = self._f32(b, N), self._f32(u, N)
+        out = np.zeros(N, dtype=np.float32)
+        if ny is None and nz is None:
+            self.L.mgo_st_residual_f32(n, _p(As32), _p(b), _p(u), _p(out))
+        else:
+            self.L.mgo_st_residual_f32_thin(n, nyv, nzv, _p(As32), _p(b), _p(u), _p(out))
         return out
 
-    def restrict32(self, nf, rf):
-        nc = (nf - 1) // 2
-        out = np.zeros(nc ** 3, dtype=np.float32)
-        self.L.mgo_st_restrict_f32(nf, _p(rf), _p(out))
+    def restrict32(self, nf, rf, nzf=None, nzc=None, nyf=None):
+        nyfv, nzfv = (nf if nyf is None else nyf), (nf if nzf is None else nzf)
+        nzcv = (nzfv - 1) // 2 if nzc is None else nzc
+        rf = self._f32(rf, nf * nyfv * nzfv)
+        out = np.zeros(((nf - 1) // 2) * ((nyfv - 1) // 2) * nzcv, dtype=np.float32)
+        if nzf is None and nzc is None and nyf is None:
+            self.L.mgo_st_restrict_f32(nf, _p(rf), _p(out))
+        else:
+            self.L.mgo_st_restrict_f32_thin(nf, nyfv, nzfv, nzcv, _p(rf), _p(out))
         return out
 
-    def prolong_add32(self, nf, uc, uf):
-        out = np.array(uf, dtype=np.float32, copy=True)
-        self.L.mgo_st_prolong_add_f32(nf, _p(uc), _p(out))
+    def prolong_add32(self, nf, uc, uf, nzf=None, nzc=None, nyf=None):
+        nyfv, nzfv = (nf if nyf is None else nyf), (nf if nzf is None else nzf)
+        nzcv = (nzfv - 1) // 2 if nzc is None else nzc
+        uc = self._f32(uc, ((nf - 1) // 2) * ((nyfv - 1) // 2) * nzcv)
+        out = np.array(self._f32(uf, nf * nyfv * nzfv), copy=True)
+        if nzf is None and nzc is None and nyf is None:
+            self.L.mgo_st_prolong_add_f32(nf, _p(uc), _p(out))
+        else:
+            self.L.mgo_st_prolong_add_f32_thin(nf, nyfv, nzfv, nzcv, _p(uc), _p(out))
         return out
 
     def vcycle_mixed(self, npts, levels, v0=3, v1=3, maxiter=100, scale=1.0, fixed_cycles=0):

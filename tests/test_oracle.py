@@ -271,3 +271,223 @@ def test_oracle_stretched_mesh_cycle_matches_committed_scipy_vectors(orc, key):
     assert np.abs(r["u"] - g["u"]).max() <= 1e-11 * np.abs(g["u"]).max()
     err = orc.error_norms_mesh(g["npts"], g["mesh"], r["u"])
     assert np.abs(np.asarray(err) / g["err"] - 1).max() <= 1e-9
+
+
+# ---- fp32 leg (mgo_f32.c): thin-grid forms, an independent binary32 restatement, float64 forward-error bounds ----
+U32 = 2.0 ** -24                      # unit roundoff of IEEE binary32 (round to nearest)
+THIN32 = [(7, 7, 7), (15, 15, 3), (31, 31, 5), (15, 7, 9), (31, 11, 3), (63, 3, 7)]     # (nx, ny, nz): cubes, thin slabs, ny != nx
+
+
+def _rand32(rng, *shape):
+    return rng.uniform(-1.0, 1.0, shape).astype(np.float32)
+
+
+def _coef_rand(rng):
+    """seven distinct coefficients of mixed sign (the level stencils have six equal off-diagonal ones, under which a swapped
+    neighbour would go unseen), diagonal dominant"""
+    As = rng.uniform(0.5, 2.0, 7) * rng.choice([-1.0, 1.0], 7)
+    As[3] = -8.0
+    return As
+
+
+def _shift(x, axis, d):
+    """x moved by d along axis with zero fill: _shift(x, 0, 1)[k] = x[k - 1]"""
+    y = np.zeros_like(x)
+    src = [slice(None)] * 3
+    dst = [slice(None)] * 3
+    if d > 0:
+        dst[axis], src[axis] = slice(d, None), slice(None, -d)
+    else:
+        dst[axis], src[axis] = slice(None, d), slice(-d, None)
+    y[tuple(dst)] = x[tuple(src)]
+    return y
+
+
+# the seven terms of a row in the canonical order {(k-1), (i-1), (j-1), C, (j+1), (i+1), (k+1)}: (axis, shift) of x
+_TERMS = [(0, 1), (1, 1), (2, 1), None, (2, -1), (1, -1), (0, -1)]
+
+
+def _np_apply32(As32, x):
+    """A x in binary32, canonical order, one rounding per multiply and per add (numpy float32 arithmetic: no FMA, no wider
+    accumulator).  Terms that fall outside the grid are skipped, not added as zeros, as in mgo_f32.c."""
+    s = np.zeros_like(x)
+    for q, t in enumerate(_TERMS):
+        if t is None:
+            s = s + As32[q] * x
+            continue
+        axis, d = t
+        inside = _shift(np.ones_like(x, dtype=bool), axis, d)
+        s = np.where(inside, s + As32[q] * _shift(x, axis, d), s)
+    return s
+
+
+def _np_jacobi32(As, scale, b, u, zero_guess=False):
+    As32, dinv = Oracle.coef32(As)
+    sc = np.float32(scale)
+    if zero_guess:
+        return sc * (b * dinv)
+    return u + sc * ((b - _np_apply32(As32, u)) * dinv)
+
+
+_W1 = np.array([0.25, 0.5, 0.25], dtype=np.float32)
+_W2 = np.array([0.0625, 0.125, 0.0625, 0.125, 0.25, 0.125, 0.0625, 0.125, 0.0625], dtype=np.float32)
+
+
+def _np_restrict32(rf, nzc):
+    nzf, nyf, nxf = rf.shape
+    nyc, nxc = (nyf - 1) // 2, (nxf - 1) // 2
+    s = np.zeros((nzc, nyc, nxc), dtype=np.float32)
+    for dk in range(3):
+        for di in range(3):
+            for dj in range(3):
+                w = _W1[dk] * _W2[di * 3 + dj]
+                pl = np.zeros((nzc, nyc, nxc), dtype=np.float32)
+                ks = [k for k in range(nzc) if 2 * k + dk < nzf]
+                pl[ks] = rf[[2 * k + dk for k in ks]][:, di:di + 2 * nyc:2, dj:dj + 2 * nxc:2]
+                inside = np.zeros((nzc, 1, 1), dtype=bool)
+                inside[ks] = True
+                s = np.where(inside, s + w * pl, s)
+    return s
+
+
+def _axis_parents(nf, nc):
+    """for every fine index: its (up to two) coarse parents in ascending order, whether each exists, and its weight"""
+    f = np.arange(nf)
+    odd = (f & 1) == 1
+    c0 = np.where(odd, (f - 1) // 2, f // 2 - 1)
+    c1 = np.where(odd, c0, f // 2)
+    w = np.where(odd, np.float32(1.0), np.float32(0.5)).astype(np.float32)
+    ok0 = (c0 >= 0) & (c0 < nc)
+    ok1 = ~odd & (c1 >= 0) & (c1 < nc)
+    return [(np.clip(c0, 0, max(nc - 1, 0)), ok0), (np.clip(c1, 0, max(nc - 1, 0)), ok1)], w
+
+
+def _np_prolong_add32(uc, uf):
+    nzf, nyf, nxf = uf.shape
+    nzc, nyc, nxc = uc.shape
+    pk, wk = _axis_parents(nzf, nzc)
+    pi, wi = _axis_parents(nyf, nyc)
+    pj, wj = _axis_parents(nxf, nxc)
+    w = wk[:, None, None] * (wi[None, :, None] * wj[None, None, :])
+    s = np.zeros_like(uf)
+    for ck, okk in pk:                 # kc ascending, then ic, then jc: the loop order of mgo_st_prolong_add_f32
+        for ci, oki in pi:
+            for cj, okj in pj:
+                ok = okk[:, None, None] & oki[None, :, None] & okj[None, None, :]
+                if uc.size:
+                    v = uc[ck[:, None, None], ci[None, :, None], cj[None, None, :]]
+                    s = np.where(ok, s + w * v, s)
+    return uf + s
+
+
+def _f64_apply_abs(As32, x):
+    """float64 values of sum_q a_q x_q and of sum_q |a_q x_q| (the products of binary32 operands are exact in float64)"""
+    a64, x64 = As32.astype(np.float64), x.astype(np.float64)
+    t, m = np.zeros_like(x64), np.zeros_like(x64)
+    for q, sh in enumerate(_TERMS):
+        v = x64 if sh is None else _shift(x64, *sh)
+        t += a64[q] * v
+        m += np.abs(a64[q] * v)
+    return t, m
+
+
+@pytest.mark.parametrize("n", [1, 3, 7, 15])
+def test_fp32_thin_forms_with_nz_equal_n_are_the_cube_forms(orc, n):
+    """the cube entry points (what mgo_vcycle_mixed calls) and the thin ones with nx = ny = nz: bit for bit"""
+    rng = np.random.default_rng(8800 + n)
+    As = orc.level_stencil(3, n + 2, 0)[0]
+    u, b = _rand32(rng, n ** 3), _rand32(rng, n ** 3)
+    for zg in (False, True):
+        assert np.array_equal(orc.jacobi32(n, As, 6.0 / 7.0, b, u, zero_guess=zg), orc.jacobi32(n, As, 6.0 / 7.0, b, u, zero_guess=zg, nz=n, ny=n))
+    assert np.array_equal(orc.residual32(n, As, b, u), orc.residual32(n, As, b, u, nz=n))
+    if n >= 3:
+        nc = (n - 1) // 2
+        uc = _rand32(rng, nc ** 3)
+        assert np.array_equal(orc.restrict32(n, u), orc.restrict32(n, u, nzf=n, nzc=nc))
+        assert np.array_equal(orc.prolong_add32(n, uc, u), orc.prolong_add32(n, uc, u, nzf=n, nzc=nc))
+
+
+@pytest.mark.parametrize("nx,ny,nz", [(7, 7, 3), (15, 7, 5), (15, 15, 1)])
+def test_fp32_thin_forms_are_a_cube_with_zero_planes_beyond(orc, nx, ny, nz):
+    """Dirichlet at z = nz: the thin sweep / residual equal the first nz planes of the same operation on a taller grid whose
+    planes nz, nz+1, .. hold zeros (a zero neighbour adds +0.0 where the thin form adds nothing: same bits for these data)"""
+    rng = np.random.default_rng(8900 + nx + ny + nz)
+    As = _coef_rand(rng)
+    u, b = _rand32(rng, nz, ny, nx), _rand32(rng, nz, ny, nx)
+    tall = nz + 2
+    U, B = np.zeros((tall, ny, nx), np.float32), np.zeros((tall, ny, nx), np.float32)
+    U[:nz], B[:nz] = u, b
+    N = nx * ny * nz
+    got = orc.jacobi32(nx, As, 0.8, b.ravel(), u.ravel(), nz=nz, ny=ny)
+    assert np.array_equal(got, orc.jacobi32(nx, As, 0.8, B.ravel(), U.ravel(), nz=tall, ny=ny)[:N])
+    got = orc.residual32(nx, As, b.ravel(), u.ravel(), nz=nz, ny=ny)
+    assert np.array_equal(got, orc.residual32(nx, As, B.ravel(), U.ravel(), nz=tall, ny=ny)[:N])
+
+
+@pytest.mark.parametrize("nx,ny,nz", THIN32)
+def test_fp32_leg_equals_a_binary32_restatement(orc, nx, ny, nz):
+    """The fp32 leg against an independent restatement in numpy float32 (IEEE binary32, one rounding per operation, no FMA): same
+    canonical order, so the same bits.  Random distinct coefficients: a swapped neighbour, a lost term, a wider accumulator or a
+    reordered sum in the oracle makes this fail."""
+    rng = np.random.default_rng(9000 + nx * ny + nz)
+    As = _coef_rand(rng)
+    sc = 6.0 / 7.0
+    u, b = _rand32(rng, nz, ny, nx), _rand32(rng, nz, ny, nx)
+    kw = dict(nz=nz, ny=ny)
+    for zg in (False, True):
+        assert np.array_equal(orc.jacobi32(nx, As, sc, b.ravel(), u.ravel(), zero_guess=zg, **kw), _np_jacobi32(As, sc, b, u, zg).ravel())
+    assert np.array_equal(orc.residual32(nx, As, b.ravel(), u.ravel(), **kw), (b - _np_apply32(Oracle.coef32(As)[0], u)).ravel())
+    nzc = (nz - 1) // 2
+    assert np.array_equal(orc.restrict32(nx, u.ravel(), nzf=nz, nzc=nzc, nyf=ny), _np_restrict32(u, nzc).ravel())
+    nzc1 = nz // 2                                             # a slab's last coarse plane without its third fine plane
+    assert np.array_equal(orc.restrict32(nx, u.ravel(), nzf=nz, nzc=nzc1, nyf=ny), _np_restrict32(u, nzc1).ravel())
+    uc = _rand32(rng, nzc, (ny - 1) // 2, (nx - 1) // 2)
+    assert np.array_equal(orc.prolong_add32(nx, uc.ravel(), u.ravel(), nzf=nz, nzc=nzc, nyf=ny), _np_prolong_add32(uc, u).ravel())
+
+
+@pytest.mark.parametrize("nx,ny,nz", THIN32 + [(255, 7, 3)])
+def test_fp32_leg_within_its_forward_error_bound(orc, nx, ny, nz):
+    """The fp32 leg against the same operations evaluated in float64 from the same binary32 inputs and the binary32-rounded
+    coefficients a_q = (float) As[q], d = (float) (1 / As[3]), s = (float) scale.  With u = 2^-24 and gamma_m = m u / (1 - m u):
+
+    sweep  o = u + s*((b - t)*d), t = sum of <= 7 products accumulated left to right.  |t^ - t| <= gamma_7 S, S = sum |a_q x_q|;
+           the subtraction, the two multiplications and the final addition add one rounding each, so to first order
+           |o^ - o| <= u |u| + gamma_10 |s d| (|b| + S) + O(u^2)  <=  16 u (|u| + |s d| (|b| + S)).
+    residual r = b - t:  |r^ - r| <= gamma_8 (|b| + S)  <=  10 u (|b| + S).
+    restriction: 27 terms w x with w = 2^-k (the product is exact), accumulated left to right: |e| <= gamma_26 sum |w x| <= 28 u sum |w x|.
+    prolongation: <= 8 terms w x (w = 1, 1/2, 1/4, 1/8: exact), sum then one add: |e| <= gamma_8 (|uf| + sum |w uc|) <= 9 u (..).
+    float64 evaluation error is ~2^-53 relative, far below these.  A missing or misplaced term (random distinct coefficients) moves
+    the result by O(1): it fails the bound.  (The bound does not see a wider accumulator; the binary32 restatement above does.)"""
+    rng = np.random.default_rng(9100 + nx * ny + nz)
+    As = _coef_rand(rng)
+    As32, d32 = Oracle.coef32(As)
+    s32 = np.float32(6.0 / 7.0)
+    u, b = _rand32(rng, nz, ny, nx), _rand32(rng, nz, ny, nx)
+    kw = dict(nz=nz, ny=ny)
+    t, S = _f64_apply_abs(As32, u)
+    sd = float(s32) * float(d32)
+    u64, b64 = u.astype(np.float64), b.astype(np.float64)
+    o = orc.jacobi32(nx, As, float(s32), b.ravel(), u.ravel(), **kw).reshape(u.shape)
+    ref = u64 + sd * (b64 - t)
+    assert np.all(np.abs(o - ref) <= 16 * U32 * (np.abs(u64) + abs(sd) * (np.abs(b64) + S))), "sweep"
+    o = orc.jacobi32(nx, As, float(s32), b.ravel(), u.ravel(), zero_guess=True, **kw).reshape(u.shape)
+    assert np.all(np.abs(o - sd * b64) <= 3 * U32 * abs(sd) * np.abs(b64)), "zero-guess sweep"
+    o = orc.residual32(nx, As, b.ravel(), u.ravel(), **kw).reshape(u.shape)
+    assert np.all(np.abs(o - (b64 - t)) <= 10 * U32 * (np.abs(b64) + S)), "residual"
+    nzc = (nz - 1) // 2
+    if nzc:
+        o = orc.restrict32(nx, u.ravel(), nzf=nz, nzc=nzc, nyf=ny).astype(np.float64)
+        ref, mag = np.zeros_like(o), np.zeros_like(o)
+        nyc, nxc = (ny - 1) // 2, (nx - 1) // 2
+        for dk in range(3):
+            for di in range(3):
+                for dj in range(3):
+                    v = float(_W1[dk]) * float(_W2[di * 3 + dj]) * u64[dk:dk + 2 * nzc:2, di:di + 2 * nyc:2, dj:dj + 2 * nxc:2].ravel()
+                    ref += v
+                    mag += np.abs(v)
+        assert np.all(np.abs(o - ref) <= 28 * U32 * mag), "restriction"
+        uc = _rand32(rng, nzc, nyc, nxc)
+        o = orc.prolong_add32(nx, uc.ravel(), u.ravel(), nzf=nz, nzc=nzc, nyf=ny).reshape(u.shape).astype(np.float64)
+        pu = _np_prolong_add32(uc.astype(np.float64), np.zeros_like(u64))          # exact in float64: <= 8 terms of 2^-k x
+        pm = _np_prolong_add32(np.abs(uc.astype(np.float64)), np.zeros_like(u64))
+        assert np.all(np.abs(o - (u64 + pu)) <= 9 * U32 * (np.abs(u64) + pm)), "prolongation"
