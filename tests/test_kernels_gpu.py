@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import Oracle
+from row_tables import _rt_apply, _rt_jacobi, _rt_tables
 
 pytestmark = pytest.mark.gpu
 RED_RTOL = 1e-13
@@ -537,36 +538,7 @@ def test_fused_residual_restrict_2d_bit_exact(mgk, orc, nf):
         mgk.free(p)
 
 
-# ---- the fused kernels on row-table operators (2-D stretched meshes) against numpy in the canonical term order ----
-def _rt_apply(ct, u):
-    """A u for the row-table operator: per grid row i the five coefficients {(i-1), W, C, E, (i+1)}, terms summed in that order"""
-    n = u.shape[0]
-    p = np.zeros((n + 2, n + 2))
-    p[1:-1, 1:-1] = u
-    t = ct[:, 0:1] * p[:-2, 1:-1]
-    t = t + ct[:, 1:2] * p[1:-1, :-2]
-    t = t + ct[:, 2:3] * p[1:-1, 1:-1]
-    t = t + ct[:, 3:4] * p[1:-1, 2:]
-    t = t + ct[:, 4:5] * p[2:, 1:-1]
-    return t
-
-
-def _rt_jacobi(ct, b, u, scale):
-    res = b - _rt_apply(ct, u)
-    return u + scale * (res * (1.0 / ct[:, 2:3]))
-
-
-def _rt_tables(rng, n):
-    q = float((n + 1) ** 2)
-    ct = np.empty((n, 5))
-    ct[:, 0] = q * rng.uniform(0.5, 1.5, n)
-    ct[:, 1] = q * rng.uniform(0.5, 1.5, n)
-    ct[:, 3] = ct[:, 1]
-    ct[:, 4] = q * rng.uniform(0.5, 1.5, n)
-    ct[:, 2] = -(ct[:, 0] + ct[:, 1] + ct[:, 3] + ct[:, 4])
-    return ct, 1.0 / ct[:, 2]
-
-
+# ---- the fused kernels on row-table operators (2-D stretched meshes) against numpy in the canonical term order (tests/row_tables.py) ----
 @pytest.mark.parametrize("n", [3, 7, 63, 255, 509, 1023, 2047])
 def test_row_table_forms_of_the_fused_2d_kernels(mgk, orc, n):
     """mgk_jacobi2_2d_rowcoef / mgk_jacobi_sumsq_rowcoef / mgk_residual_sumsq_rowcoef / mgk_prolong_jacobi_rowcoef /
