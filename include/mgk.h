@@ -256,6 +256,11 @@ int  mgk_tail_cycle_f64(mgk_ctx *ctx, const mgk_geom *g0, int nlev, const int *n
                         double scale, int v0, int v1, const double *b, double *u, void *stream);
 int  mgk_tail_cycle_f32(mgk_ctx *ctx, const mgk_geom *g0, int nlev, const int *n, const double *coef7, const double *dinv,
                         double scale, int v0, int v1, const float *b, float *u, void *stream);
+/* full multigrid FMG(nu) on the same levels in one launch (fp64, nlev >= 2): b_l = R b_{l-1} down the levels, v1 sweeps from the zero
+ * guess on the last one, then for each level r from the second-coarsest up to the first: u_r = 0 + P u_{r+1} and nu V-cycles on the
+ * levels r .. nlev-1 from that guess (v0 sweeps on r, the cycle of mgk_tail_cycle_f64 below it).  u: the first level's result. */
+int  mgk_tail_fmg_f64(mgk_ctx *ctx, const mgk_geom *g0, int nlev, const int *n, const double *coef7, const double *dinv,
+                      double scale, int v0, int v1, int nu, const double *b, double *u, void *stream);
 /* ... with its own damping factor on the COARSEST level (2-D fp64; either coef7 + dinv or the row tables ctab + dtab, the other pair NULL):
  * PCMG's exact coarse solve on a 1 x 1 grid is one undamped Jacobi sweep from the zero guess (v1 = 1, coarse_scale = 1) */
 int  mgk_tail_cycle_cs_f64(mgk_ctx *ctx, const mgk_geom *g0, int nlev, const int *n, const double *coef7, const double *dinv,
@@ -326,6 +331,12 @@ int  mgk_jacobi2_sumsq_mid_f64(mgk_ctx *ctx, const mgk_geom *g, const double *co
 int  mgk_prolong_jacobi2_ok_f64(const mgk_geom *gf, const mgk_geom *gc);
 int  mgk_prolong_jacobi2_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
                              const double *b, const double *uc, const double *u, double *unew, void *stream);
+/* full multigrid (FMG) interpolation: unew = J(J(0 + P uc)) -- the coarse solution interpolated as the new iterate (the old unew is never
+ * read) and the first two pre-smoothing sweeps of the V-cycle that starts from it, 17 B per unknown.  Equals a zeroed field +
+ * mgk_prolong_add_f64 + two mgk_jacobi_f64 sweeps bit for bit.  Shapes of mgk_prolong_jacobi2_f64; _ok_ tells. */
+int  mgk_interp_jacobi2_ok_f64(const mgk_geom *gf, const mgk_geom *gc);
+int  mgk_interp_jacobi2_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
+                            const double *b, const double *uc, double *unew, void *stream);
 /* THREE sweeps from a zero initial guess in one pass that reads b alone (the first one is pointwise: mgk_jacobi_zero_*):
  * unew = J(J(J0(b))) -- the whole of a pre-smoothing KSPSolve with max_it = 3 on a coarse level (src/solver.c:1536), 16 B per unknown
  * (fp32: 8) instead of 8 + 24.  Whole 3-D grids of full-row shape: fp32 n = 255 .. 1023, fp64 n = 127 .. 1023; _ok_ tells (1 / 0). */
@@ -460,6 +471,9 @@ int  mgk_jacobi3_2d_zero_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef
 int  mgk_prolong_jacobi3_2d_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
                                 const double *ctab, const double *dtab, const double *b, const double *uc, const double *u, double *unew,
                                 void *stream);
+/* FMG interpolation, 2-D, uniform mesh: unew = J(J(J(0 + P uc))) (the old unew is never read), 18 B per unknown; any 2-D grid */
+int  mgk_interp_jacobi3_2d_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
+                               const double *b, const double *uc, double *unew, void *stream);
 
 /* the same in 3-D (whole grids, any vertex-centred shape): unew = J(J(J(u))) [and *sumsq_host = || b - A u ||^2 of the input field] in one
  * pass, 24 B per unknown.  Independent waves, one per SIMD (up to 512 registers per lane), 120 x 4 point columns per wave marching along z. */

@@ -96,6 +96,13 @@ int  mg_solver_reset(mg_solver *s);
 int  mg_solver_solve(mg_solver *s);
 /* exactly `ncycles` more V-cycles from the current state (no stopping test); used by bench.py */
 int  mg_solver_cycles(mg_solver *s, int ncycles);
+/* full multigrid FMG(nu) (PETSc's -pc_mg_type full) on the current right-hand side: b_l = R b_{l-1} down the levels, v1 sweeps from the
+ * zero guess on the coarsest, then on each finer level l: u_l = 0 + P u_{l+1} and nu V-cycles on the levels l .. L-1 from that guess.
+ * Leaves the solver as one iteration would (rnorm[0] = ||b||, rnorm[1] = ||b - A u0||, iterations = 1); mg_solver_cycles continues
+ * with V-cycles from u0.  One GPU, fp64, Richardson + Jacobi, uniform mesh, levels >= 2, nu >= 1: anything else returns MGK_EINVAL. */
+int  mg_solver_fmg(mg_solver *s, int nu);
+/* FMG(nu), then V-cycles under the stop rule of mg_solver_solve; solve_seconds covers both */
+int  mg_solver_solve_fmg(mg_solver *s, int nu);
 /* block until every stream of this solver's device is idle */
 int  mg_solver_sync(mg_solver *s);
 

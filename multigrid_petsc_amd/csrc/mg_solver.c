@@ -15,6 +15,7 @@
  */
 #include "mgsolve.h"
 #include "mg_comm.h"
+#include "mg_solver_internal.h"
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -22,9 +23,6 @@
 #include <time.h>
 
 #define MG_PI 3.14159265358979323846   /* include/problem.h:13 */
-#define MG_MAX_LEVELS 32
-#define MG_MAX_TIMERS 4096
-
 static __thread char g_mgerr[512] = "ok";
 const char *mg_last_error(void) { return g_mgerr; }
 static int mgfail(int code, const char *what) {
@@ -32,35 +30,6 @@ static int mgfail(int code, const char *what) {
     return code;
 }
 #define CHK(call) do { int rc_ = (call); if (rc_) return mgfail(rc_, #call); } while (0)
-
-/* the fields of one level in one precision (index 0: fp64, 1: fp32) */
-typedef struct mg_fset {
-    mgk_geom g;             /* local geometry in elements of that precision */
-    void *u, *b, *rv, *tmp;
-    int guess_nonzero;      /* KSPSetInitialGuessNonzero state of ksp[l] (src/solver.c:1532,1537,1543) */
-    int u_ghost_ok;         /* z ghost planes of `u` hold the neighbours' current boundary planes */
-    int u_ghost_pending;    /* ... but the exchange is still in flight on the comm stream */
-    int jz_ready;           /* tmp already holds the first sweep from a zero guess (written by the fused residual+restriction) */
-    int last_sweep_pending; /* pre-smoothing stopped one sweep short: the restriction that follows makes it (mgk_sweep_residual_restrict_f64) */
-    int b_ghost_ok;         /* z ghost planes of `b` hold the neighbours' boundary planes (two-sweep passes on slabs) */
-    void *far;              /* distributed levels: field of geometry gfar = (nx, ny, 2) for the neighbours' SECOND planes of u */
-    void *far2, *bfar;      /* fp64, fuse bit 10: same geometry; hi ghost = the rank above's THIRD plane of u / SECOND plane of b (sweep fused
-                             * with residual + restriction on a slab: mgk_sweep_residual_restrict_slab_f64) */
-    int bfar_ok;            /* bfar's hi ghost plane is valid (b of a level changes only when the restriction above rewrites it) */
-    mgk_geom gfar;
-} mg_fset;
-
-typedef struct mg_level {
-    int n;                  /* unknowns per side of the whole grid */
-    int z0, nzl;            /* owned planes [z0, z0+nzl) (3-D); whole grid when replicated / 2-D */
-    int nz_min;             /* fewest planes any rank owns on this level: every choice between code paths that differ in their
-                             * exchanges is made on it, never on the own slab size, so that all ranks take the same path */
-    int distributed;
-    double coef[7], dinv, h;
-    double *ctab, *dtab;    /* -mesh 1/2 (2-D): device tables, 5 coefficients {(i-1), W, C, E, (i+1)} and 1/diag per grid row */
-    mg_fset f[2];
-    double *p2;             /* Chebyshev: third recurrence vector (fp64) */
-} mg_level;
 
 /* the kernel ABI of one precision behind untyped pointers: the cycle code below is written once */
 typedef struct mg_ops {
@@ -124,42 +93,6 @@ W32(tc)(mgk_ctx *c, const mgk_geom *g0, int nl, const int *n, const double *k7, 
 static const mg_ops OPS[2] = {
     {8, jr_64, jz_64, rs_64, rf_64, pa_64, pj_64, rr_64, rg_64, fin_64, rrz_64, j2_64, j2s_64, pjr_64, rrr_64, rrs_64, tc_64},
     {4, jr_32, jz_32, rs_32, rf_32, pa_32, pj_32, rr_32, rg_32, fin_32, rrz_32, j2_32, j2s_32, pjr_32, rrr_32, rrs_32, tc_32},
-};
-
-struct mg_solver {
-    mg_config cfg;
-    mgk_ctx *ctx;
-    mg_comm *comm;
-    int levels, ldist;      /* ldist: number of distributed (finest) levels; 0 when nranks == 1 */
-    mg_level L[MG_MAX_LEVELS];
-    int *zstart;            /* plane starts of the first replicated level's producers (nranks+1) */
-    double *rnorm;          /* maxiter+1 */
-    int rnorm_cap;
-    int iter;
-    double bnorm, rchk;
-    int started;
-    int deferring;          /* mg_solver_cycles: norms are deposited on the device and read once at the end */
-    double *d_norms; int d_norms_cap;
-    double *pin; int pin_cap; /* pinned host landing area of the reduced norms */
-    int spec_valid;         /* > 0: level-0 tmp holds that many sweeps of u, made by the sweep(s)+norm kernel that closed the last cycle */
-    int sweep_owed;         /* fuse bit 12: the post-smoothing of level 0 stopped one sweep short (prolongation + two sweeps in one pass); the
-                             * pass that evaluates the norm makes that sweep first */
-    int last_cycle;         /* the caller knows (fixed cycle count) or expects (contraction so far) that this cycle is the last one: no sweep is
-                             * owed and no speculative sweep is made -- the norm comes from the store-free residual + norm pass */
-    int iterate_behind;     /* ... and after that pass u is still ONE sweep behind the iterate the norm belongs to (it was never stored:
-                             * tmp holds the sweep after it); finalize_iterate() makes the sweep if the iteration stops here */
-    double solve_seconds;
-    int lgraph;             /* levels >= lgraph form the launch-bound coarse part replayed as one HIP graph (0: off) */
-    int ltail;              /* levels >= ltail (n <= 15 in 3-D, <= 63 in 2-D) run as ONE kernel with their fields in LDS (0: off) */
-    void *coarse_graph[2];  /* one recording per precision */
-    void *graph_u[2], *graph_tmp[2];   /* u / tmp of the level that feeds the recording, as the recorded kernels know them */
-    int graph_rerecorded;   /* recordings thrown away because those pointers had changed (0 in every default configuration) */
-    /* profiling */
-    int prof_on, prof_n;
-    void *timers[MG_MAX_TIMERS];
-    unsigned char timer_kind[MG_MAX_TIMERS];
-    int prof_kind;          /* kind of the next timer: 0 plain sweep, 1 two sweeps in one pass */
-    int ntimers_created;
 };
 
 /* ------------------------------------------------------------------ */
@@ -820,6 +753,11 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
     }
     int it0 = 0;
     F->last_sweep_pending = 0;
+    if (F->pre_done) {
+        /* FMG: the interpolation kernel made the first sweeps from the interpolated guess (mg_fmg.c sets this only when they fit) */
+        if (F->guess_nonzero && maxit >= F->pre_done) it0 = F->pre_done;
+        F->pre_done = 0;
+    }
     if (l == 0 && P == 0 && s->spec_valid && maxit >= s->spec_valid && F->guess_nonzero) {
         /* the first sweep(s) were already made by the kernel that evaluated the previous cycle's residual norm */
         swap_ptr(&F->u, &F->tmp);
@@ -1597,7 +1535,7 @@ static int start(mg_solver *s) {
     CHK(mgk_sumsq_f64(s->ctx, &F->g, (const double *)F->b, &ss, NULL)); /* VecNorm(b[0]) :1512 */
     CHK(norm_from_sumsq(s, ss, &s->bnorm));
     for (int l = 0; l < s->levels; l++)
-        for (int p = 0; p < 2; p++) { s->L[l].f[p].guess_nonzero = 0; s->L[l].f[p].u_ghost_ok = 0; s->L[l].f[p].u_ghost_pending = 0; s->L[l].f[p].b_ghost_ok = 0; s->L[l].f[p].jz_ready = 0; s->L[l].f[p].last_sweep_pending = 0; s->L[l].f[p].bfar_ok = 0; }
+        for (int p = 0; p < 2; p++) { s->L[l].f[p].guess_nonzero = 0; s->L[l].f[p].u_ghost_ok = 0; s->L[l].f[p].u_ghost_pending = 0; s->L[l].f[p].b_ghost_ok = 0; s->L[l].f[p].jz_ready = 0; s->L[l].f[p].last_sweep_pending = 0; s->L[l].f[p].bfar_ok = 0; s->L[l].f[p].pre_done = 0; }
     CHK(mgk_memset0(s->ctx, F->u, sizeof(double) * (size_t)F->g.total, NULL));   /* VecSet(u[0],0) :1514 */
     /* rv = A u - b with u = 0 (:1516-1517); ||A u - b|| = ||b - A u||, evaluated by the same residual kernel */
     if (s->cfg.precision == MG_PREC_MIXED)
@@ -1619,10 +1557,8 @@ static double wall(void) {
     return t.tv_sec + 1e-9 * t.tv_nsec;
 }
 
-int mg_solver_solve(mg_solver *s) {
-    CHK(start(s));
-    CHK(mgk_sync(s->ctx, NULL));
-    double t0 = wall();                                                  /* MPI_Wtime :1526 */
+/* the while loop of src/solver.c:1530-1550 from the current state */
+int mgi_iterate(mg_solver *s) {
     const int devnorm = s->cfg.nranks > 1 && s->comm->allreduce_sum_dev != NULL;
     if (devnorm) CHK(need_slots(s, 1));
     while (s->iter < s->cfg.maxiter && 100000000 * s->bnorm > s->rchk && s->rchk > s->cfg.rtol * s->bnorm) {   /* :1530 */
@@ -1645,6 +1581,14 @@ int mg_solver_solve(mg_solver *s) {
         s->rchk = sqrt(ss);
         if (s->iter < s->rnorm_cap) s->rnorm[s->iter] = s->rchk;
     }
+    return 0;
+}
+
+int mg_solver_solve(mg_solver *s) {
+    CHK(start(s));
+    CHK(mgk_sync(s->ctx, NULL));
+    double t0 = wall();                                                  /* MPI_Wtime :1526 */
+    CHK(mgi_iterate(s));
     CHK(finalize_iterate(s));
     CHK(mgk_sync(s->ctx, NULL));
     s->solve_seconds = wall() - t0;                                      /* :1553 */
@@ -1714,4 +1658,32 @@ double mg_solver_dof_updates_per_cycle(const mg_solver *s) {
         tot += sweeps * N;
     }
     return tot;
+}
+
+/* ------------------------------------------------------------------ */
+/* steps for the full-multigrid driver (mg_fmg.c; mg_solver_internal.h) */
+/* ------------------------------------------------------------------ */
+int mgi_fail(int code, const char *what) { return mgfail(code, what); }
+double mgi_wall(void) { return wall(); }
+int mgi_start(mg_solver *s) { return start(s); }
+int mgi_smooth(mg_solver *s, int l, int maxit) { return smooth(s, 0, l, maxit, 0); }
+int mgi_vcycle_once(mg_solver *s) { return vcycle_once(s); }
+int mgi_finalize(mg_solver *s) { return finalize_iterate(s); }
+
+/* one iteration of the reference's loop (src/solver.c:1531-1543) on the levels l .. L-1 alone, level l in the role of level 0: v0 sweeps on
+ * l from the guess in u_l (its KSP keeps the non-zero guess), the descent and the ascent as in cycle_body -- the tail kernel when l lies
+ * above the tail, per-level launches otherwise -- but never the coarse-level graph (whose recording starts at level 0's cycle) */
+int mgi_vcycle_rooted(mg_solver *s, int l) {
+    const int levels = s->levels, lt = s->ltail;
+    if (l < 1 || l >= levels - 1) return mgfail(MGK_EINVAL, "mgi_vcycle_rooted: root must be 1 .. levels-2");
+    if (lt && l >= lt) s->ltail = 0;                                    /* rooted inside the tail: its levels one by one */
+    const int lend = s->ltail ? s->ltail : levels - 1;
+    int rc = smooth(s, 0, l, s->cfg.v[0], 1);
+    for (int q = l + 1; q <= lend && !rc; q++) rc = descend(s, 0, q);
+    for (int q = lend - 1; q >= l && !rc; q--) {
+        rc = prolong_smooth(s, 0, q);
+        if (q != l) s->L[q].f[0].guess_nonzero = 0;
+    }
+    s->ltail = lt;
+    return rc;
 }

@@ -1,0 +1,91 @@
+/*
+ * mg_solver_internal.h -- the solver's state and the cycle steps that the full-multigrid driver (mg_fmg.c) builds on.  Private to
+ * libmgpetsc.so: not installed, not part of the C API (include/mgsolve.h).  Everything declared here is DEFINED in mg_solver.c, which
+ * references no symbol of mg_fmg.c (the host tests link mg_solver.c without it, against a mock of the kernel ABI).
+ */
+#ifndef MG_SOLVER_INTERNAL_H
+#define MG_SOLVER_INTERNAL_H
+#include "mgsolve.h"
+#include "mg_comm.h"
+
+#define MG_MAX_LEVELS 32
+#define MG_MAX_TIMERS 4096
+
+
+/* the fields of one level in one precision (index 0: fp64, 1: fp32) */
+typedef struct mg_fset {
+    mgk_geom g;             /* local geometry in elements of that precision */
+    void *u, *b, *rv, *tmp;
+    int guess_nonzero;      /* KSPSetInitialGuessNonzero state of ksp[l] (src/solver.c:1532,1537,1543) */
+    int u_ghost_ok;         /* z ghost planes of `u` hold the neighbours' current boundary planes */
+    int u_ghost_pending;    /* ... but the exchange is still in flight on the comm stream */
+    int jz_ready;           /* tmp already holds the first sweep from a zero guess (written by the fused residual+restriction) */
+    int last_sweep_pending; /* pre-smoothing stopped one sweep short: the restriction that follows makes it (mgk_sweep_residual_restrict_f64) */
+    int b_ghost_ok;         /* z ghost planes of `b` hold the neighbours' boundary planes (two-sweep passes on slabs) */
+    int pre_done;           /* FMG (mg_fmg.c): u already holds the first pre_done sweeps of the next smoothing from a non-zero guess (made by the
+                             * interpolation kernel); smooth() starts after them */
+    void *far;              /* distributed levels: field of geometry gfar = (nx, ny, 2) for the neighbours' SECOND planes of u */
+    void *far2, *bfar;      /* fp64, fuse bit 10: same geometry; hi ghost = the rank above's THIRD plane of u / SECOND plane of b (sweep fused
+                             * with residual + restriction on a slab: mgk_sweep_residual_restrict_slab_f64) */
+    int bfar_ok;            /* bfar's hi ghost plane is valid (b of a level changes only when the restriction above rewrites it) */
+    mgk_geom gfar;
+} mg_fset;
+
+typedef struct mg_level {
+    int n;                  /* unknowns per side of the whole grid */
+    int z0, nzl;            /* owned planes [z0, z0+nzl) (3-D); whole grid when replicated / 2-D */
+    int nz_min;             /* fewest planes any rank owns on this level: every choice between code paths that differ in their
+                             * exchanges is made on it, never on the own slab size, so that all ranks take the same path */
+    int distributed;
+    double coef[7], dinv, h;
+    double *ctab, *dtab;    /* -mesh 1/2 (2-D): device tables, 5 coefficients {(i-1), W, C, E, (i+1)} and 1/diag per grid row */
+    mg_fset f[2];
+    double *p2;             /* Chebyshev: third recurrence vector (fp64) */
+} mg_level;
+
+struct mg_solver {
+    mg_config cfg;
+    mgk_ctx *ctx;
+    mg_comm *comm;
+    int levels, ldist;      /* ldist: number of distributed (finest) levels; 0 when nranks == 1 */
+    mg_level L[MG_MAX_LEVELS];
+    int *zstart;            /* plane starts of the first replicated level's producers (nranks+1) */
+    double *rnorm;          /* maxiter+1 */
+    int rnorm_cap;
+    int iter;
+    double bnorm, rchk;
+    int started;
+    int deferring;          /* mg_solver_cycles: norms are deposited on the device and read once at the end */
+    double *d_norms; int d_norms_cap;
+    double *pin; int pin_cap; /* pinned host landing area of the reduced norms */
+    int spec_valid;         /* > 0: level-0 tmp holds that many sweeps of u, made by the sweep(s)+norm kernel that closed the last cycle */
+    int sweep_owed;         /* fuse bit 12: the post-smoothing of level 0 stopped one sweep short (prolongation + two sweeps in one pass); the
+                             * pass that evaluates the norm makes that sweep first */
+    int last_cycle;         /* the caller knows (fixed cycle count) or expects (contraction so far) that this cycle is the last one: no sweep is
+                             * owed and no speculative sweep is made -- the norm comes from the store-free residual + norm pass */
+    int iterate_behind;     /* ... and after that pass u is still ONE sweep behind the iterate the norm belongs to (it was never stored:
+                             * tmp holds the sweep after it); finalize_iterate() makes the sweep if the iteration stops here */
+    double solve_seconds;
+    int lgraph;             /* levels >= lgraph form the launch-bound coarse part replayed as one HIP graph (0: off) */
+    int ltail;              /* levels >= ltail (n <= 15 in 3-D, <= 63 in 2-D) run as ONE kernel with their fields in LDS (0: off) */
+    void *coarse_graph[2];  /* one recording per precision */
+    void *graph_u[2], *graph_tmp[2];   /* u / tmp of the level that feeds the recording, as the recorded kernels know them */
+    int graph_rerecorded;   /* recordings thrown away because those pointers had changed (0 in every default configuration) */
+    /* profiling */
+    int prof_on, prof_n;
+    void *timers[MG_MAX_TIMERS];
+    unsigned char timer_kind[MG_MAX_TIMERS];
+    int prof_kind;          /* kind of the next timer: 0 plain sweep, 1 two sweeps in one pass */
+    int ntimers_created;
+};
+
+/* the steps of mg_solver.c, for mg_fmg.c (fp64, one rank) */
+int    mgi_fail(int code, const char *what);            /* records the message for mg_last_error(), returns code */
+double mgi_wall(void);
+int    mgi_start(mg_solver *s);                          /* src/solver.c:1512-1523: ||b||, u0 = 0, rnorm[0], every level flag reset, iter = 0 */
+int    mgi_smooth(mg_solver *s, int l, int maxit);       /* KSPSolve on level l (guess as L[l].f[0].guess_nonzero says), no restriction follows */
+int    mgi_vcycle_rooted(mg_solver *s, int l);           /* one V-cycle on the levels l .. L-1 (l >= 1) from the guess in u_l, without the graph */
+int    mgi_vcycle_once(mg_solver *s);                    /* one iteration of the solve loop (cycle rooted at level 0 + the norm), iter += 1 */
+int    mgi_iterate(mg_solver *s);                        /* the solve loop under the stop rule of src/solver.c:1530, from the current state */
+int    mgi_finalize(mg_solver *s);                       /* materialise the iterate the last norm belongs to */
+#endif

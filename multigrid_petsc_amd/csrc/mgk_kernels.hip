@@ -1867,7 +1867,9 @@ __global__ void __launch_bounds__(64 * WX) k_pj2r(const PJ2Args a) {
         for (int rr = 0; rr < R1; rr++) { VT tmpv = ua[rr]; ua[rr] = ub[rr]; ub[rr] = uc[rr]; uc[rr] = tmpv; }
     }
 }
-template <int WX, bool SLAB>
+// ZU (FMG interpolation, mgk_interp_jacobi2_f64): the old u is not read -- every plane of it counts as zero, so the pass makes
+// J(J(0 + P uc)) from b and uc alone (17 instead of 25 B per unknown); the correction adds to 0.0 exactly as mgk_prolong_add_f64 on a zeroed field
+template <int WX, bool SLAB, bool ZU = false>
 __global__ void __launch_bounds__(64 * WX) k_pj2r3(const PJ2Args a) {
     typedef double T;
     constexpr int VX = 2, TY = 4, R1 = TY + 4, R2 = TY + 2, TX = 64 * VX * WX, LW = TX + 2 * VX, NCR = 5, LC = 64 * WX + 4;
@@ -1965,7 +1967,10 @@ __global__ void __launch_bounds__(64 * WX) k_pj2r3(const PJ2Args a) {
         const auto r0 = URS(t0), r1 = URS(t0 + 1), r2 = URS(t0 + 2);
         const auto rb = BRS(t0 + 1);
 #pragma unroll
-        for (int rr = 0; rr < R1; rr++) { ua[rr] = bufld<T>(r0, lb, urb[rr]); ub[rr] = bufld<T>(r1, lb, urb[rr]); uc[rr] = bufld<T>(r2, lb, urb[rr]); }
+        for (int rr = 0; rr < R1; rr++) {
+            if (ZU) { ua[rr] = v16_zero<T>(); ub[rr] = ua[rr]; uc[rr] = ua[rr]; }
+            else { ua[rr] = bufld<T>(r0, lb, urb[rr]); ub[rr] = bufld<T>(r1, lb, urb[rr]); uc[rr] = bufld<T>(r2, lb, urb[rr]); }
+        }
 #pragma unroll
         for (int q = 0; q < R2; q++) { b1[q] = bufld<T>(rb, lb, brb[q]); bn[q] = v16_zero<T>(); }
         stc(c0, m - 2); stc(c1, m - 1); stc(c2, m);
@@ -2038,7 +2043,7 @@ __global__ void __launch_bounds__(64 * WX) k_pj2r3(const PJ2Args a) {
         {
             const auto r3 = URS(t + 3);
 #pragma unroll
-            for (int rr = 0; rr < R1; rr++) ua[rr] = bufld<T>(r3, lb, urb[rr]);
+            for (int rr = 0; rr < R1; rr++) ua[rr] = ZU ? v16_zero<T>() : bufld<T>(r3, lb, urb[rr]);
         }
         // ---- second sweep of plane t ----
         if (t >= z0) {
@@ -2091,12 +2096,12 @@ extern "C" int mgk_prolong_jacobi2_ok_f64(const mgk_geom *gf, const mgk_geom *gc
     const int w = (gf->nx + 1) / 128;
     return (w == 4 || w == 8) ? 1 : 0;                                         // rows of 512 / 1024 (n = 511, 1023)
 }
-// unew = J(J(u + P uc)): the prolongation, its correction and the first two post-smoothing sweeps in one pass
-extern "C" int mgk_prolong_jacobi2_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
-                                       const double *b, const double *uc, const double *u, double *unew, void *stream) {
-    if (!c || !coef || !b || !uc || !u || !unew || u == unew || !mgk_prolong_jacobi2_ok_f64(gf, gc)) return fail(MGK_EINVAL, "mgk_prolong_jacobi2_f64: bad arguments / shape not built");
+// unew = J(J(u + P uc)) (ZU: J(J(0 + P uc)), u not read): one launch of the whole-grid form
+template <bool ZU>
+static int prolong_jacobi2(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
+                           const double *b, const double *uc, const double *u, double *unew, void *stream) {
     PJ2Args a; memset(&a, 0, sizeof(a));
-    a.u = u + gf->org; a.b = b + gf->org; a.uc = uc + gc->org; a.out = unew + gf->org;
+    a.u = ZU ? nullptr : u + gf->org; a.b = b + gf->org; a.uc = uc + gc->org; a.out = unew + gf->org;
     a.nx = gf->nx; a.ny = gf->ny; a.nz = gf->nz; a.nxc = gc->nx; a.nyc = gc->ny; a.nzc = gc->nz;
     a.rs = gf->pitch; a.ms = gf->plane; a.crs = gc->pitch; a.cms = gc->plane;
     a.a0 = coef[0]; a.a1 = coef[1]; a.a2 = coef[2]; a.a3 = coef[3]; a.a4 = coef[4]; a.a5 = coef[5]; a.a6 = coef[6];
@@ -2110,7 +2115,10 @@ extern "C" int mgk_prolong_jacobi2_f64(mgk_ctx *c, const mgk_geom *gf, const mgk
     if (zc < 8) zc = 8;
     a.zc = zc;
     const unsigned nblk = (unsigned)(a.nty * ((gf->nz + zc - 1) / zc));
-    if ((gf->nx + 1) / 128 == 4 && g_variant != 46) hipLaunchKernelGGL((k_pj2r3<4, false>), dim3(nblk), dim3(256), 0, S(c, stream), a);   // round 3: the unrolled form on rows of
+    if (ZU) {                                                    // (the unrolled form only)
+        if ((gf->nx + 1) / 128 == 4) hipLaunchKernelGGL((k_pj2r3<4, false, true>), dim3(nblk), dim3(256), 0, S(c, stream), a);
+        else hipLaunchKernelGGL((k_pj2r3<8, false, true>), dim3(nblk), dim3(512), 0, S(c, stream), a);
+    } else if ((gf->nx + 1) / 128 == 4 && g_variant != 46) hipLaunchKernelGGL((k_pj2r3<4, false>), dim3(nblk), dim3(256), 0, S(c, stream), a);   // round 3: the unrolled form on rows of
                                                                                                         // 512 too: 511^3 0.651 -> 0.601 ms (253 VGPRs, two blocks per CU)
     else if ((gf->nx + 1) / 128 == 4) hipLaunchKernelGGL((k_pj2r<4>), dim3(nblk), dim3(256), 0, S(c, stream), a);
     else if (g_variant != 46) hipLaunchKernelGGL((k_pj2r3<8, false>), dim3(nblk), dim3(512), 0, S(c, stream), a);      // marching loop unrolled by three, the plane roles
@@ -2118,6 +2126,20 @@ extern "C" int mgk_prolong_jacobi2_f64(mgk_ctx *c, const mgk_geom *gf, const mgk
     else hipLaunchKernelGGL((k_pj2r<8>), dim3(nblk), dim3(512), 0, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
+}
+// unew = J(J(u + P uc)): the prolongation, its correction and the first two post-smoothing sweeps in one pass
+extern "C" int mgk_prolong_jacobi2_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
+                                       const double *b, const double *uc, const double *u, double *unew, void *stream) {
+    if (!c || !coef || !b || !uc || !u || !unew || u == unew || !mgk_prolong_jacobi2_ok_f64(gf, gc)) return fail(MGK_EINVAL, "mgk_prolong_jacobi2_f64: bad arguments / shape not built");
+    return prolong_jacobi2<false>(c, gf, gc, coef, dinv, scale, b, uc, u, unew, stream);
+}
+// FMG interpolation (full multigrid): unew = J(J(0 + P uc)) -- the interpolated coarse solution as the new iterate and the first two
+// pre-smoothing sweeps of the V-cycle that starts from it, in one pass over b and uc (the old unew is never read).  Same shapes as above
+extern "C" int mgk_interp_jacobi2_ok_f64(const mgk_geom *gf, const mgk_geom *gc) { return mgk_prolong_jacobi2_ok_f64(gf, gc); }
+extern "C" int mgk_interp_jacobi2_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
+                                      const double *b, const double *uc, double *unew, void *stream) {
+    if (!c || !coef || !b || !uc || !unew || unew == b || !mgk_interp_jacobi2_ok_f64(gf, gc)) return fail(MGK_EINVAL, "mgk_interp_jacobi2_f64: bad arguments / shape not built");
+    return prolong_jacobi2<true>(c, gf, gc, coef, dinv, scale, b, uc, nullptr, unew, stream);
 }
 
 // The same on a z-slab of a multi-GPU run, output planes [zbeg, zend) (zbeg even).  u's and b's ghost planes hold the neighbours' boundary planes
@@ -5217,13 +5239,96 @@ __global__ void __launch_bounds__(1024) k_tail(const TailArgs<T> a) {
     if (a.stamps && threadIdx.x == 0) a.stamps[256] = nstamp;
 }
 
+// Full multigrid on the tail levels (mgk_tail_fmg_f64), one launch: b of the first tail level comes in, the FMG restriction chain
+// b_l = R b_{l-1} runs down, the coarsest level gets v1 sweeps from the zero guess, and for every root r = nlev-2 .. 0: u_r = 0 + P u_{r+1}
+// (level r's arrays are untouched until its stage: A0 is still all zeros), then nu V-cycles on the levels r .. nlev-1 -- v0 sweeps on r from
+// that guess, residual + restriction + zero-guess sweeps down, prolongation + v0 sweeps up (the operations of k_tail, in the order of the
+// host's cycle).  u of the first tail level goes out.
+template <typename T, int DIM>
+__global__ void __launch_bounds__(1024) k_tail_fmg(const TailArgs<T> a, int nu) {
+    __shared__ __attribute__((aligned(16))) unsigned char raw[MGK_TAIL_LDS_BYTES];
+    T *lds = reinterpret_cast<T *>(raw);
+    for (int q = threadIdx.x; q < a.total; q += blockDim.x) lds[q] = (T)0;        // ghost rings stay 0 (homogeneous Dirichlet)
+    __syncthreads();
+    int cur[MGK_TAIL_MAXLEV];
+    auto A = [&](int l, int which) -> T * { const int m = a.n[l] + 2; const int sz = (DIM == 3) ? m * m * m : m * m; return lds + a.off[l] + which * sz; };
+    auto Bv = [&](int l) -> T * { return A(l, 2); };
+    {
+        const int n = a.n[0], m = n + 2, N = (DIM == 3) ? n * n * n : n * n;
+        T *b0 = Bv(0);
+        for (int p = threadIdx.x; p < N; p += blockDim.x) {
+            const int j = p % n, i = (p / n) % n, k = (DIM == 3) ? p / (n * n) : 0;
+            b0[tail_idx<T, DIM>(m, k, i, j)] = a.b_in[(long)k * a.ms + (long)i * a.rs + j];
+        }
+    }
+    __syncthreads();
+    for (int l = 1; l < a.nlev; l++) {            // b_l = R b_{l-1}
+        tail_restrict<T, DIM>(a.n[l - 1], a.n[l], Bv(l - 1), Bv(l));
+        __syncthreads();
+    }
+    // KSPSolve from a zero guess: the first sweep is scale*(b*dinv); with no sweep at all the level is zero-filled (A0 may hold an earlier stage's u)
+    auto smooth0 = [&](int l, int sweeps) {
+        cur[l] = 0;
+        const T sc = (l == a.nlev - 1) ? a.cscale : a.scale;
+        if (sweeps < 1) {
+            tail_points<DIM>(a.n[l], [&](int k, int i, int j) { A(l, 0)[tail_idx<T, DIM>(a.n[l] + 2, k, i, j)] = (T)0; });
+            __syncthreads();
+            return;
+        }
+        tail_stencil<T, DIM>(2, a.n[l], a.coef[l], a.dinv[l], sc, A(l, 0), Bv(l), A(l, 0));
+        __syncthreads();
+        for (int it = 1; it < sweeps; it++) {
+            tail_stencil<T, DIM>(0, a.n[l], a.coef[l], a.dinv[l], sc, A(l, cur[l]), Bv(l), A(l, cur[l] ^ 1));
+            __syncthreads();
+            cur[l] ^= 1;
+        }
+    };
+    auto sweeps = [&](int l, int count) {         // from the guess in A(l, cur[l])
+        for (int it = 0; it < count; it++) {
+            tail_stencil<T, DIM>(0, a.n[l], a.coef[l], a.dinv[l], a.scale, A(l, cur[l]), Bv(l), A(l, cur[l] ^ 1));
+            __syncthreads();
+            cur[l] ^= 1;
+        }
+    };
+    smooth0(a.nlev - 1, a.v1);
+    for (int r = a.nlev - 2; r >= 0; r--) {
+        cur[r] = 0;
+        tail_prolong_add<T, DIM>(a.n[r], a.n[r + 1], A(r + 1, cur[r + 1]), A(r, 0));    // 0 + P u_{r+1}
+        __syncthreads();
+        for (int c = 0; c < nu; c++) {
+            sweeps(r, a.v0);
+            for (int l = r + 1; l < a.nlev; l++) {
+                tail_stencil<T, DIM>(1, a.n[l - 1], a.coef[l - 1], a.dinv[l - 1], a.scale, A(l - 1, cur[l - 1]), Bv(l - 1), A(l - 1, cur[l - 1] ^ 1));
+                __syncthreads();
+                tail_restrict<T, DIM>(a.n[l - 1], a.n[l], A(l - 1, cur[l - 1] ^ 1), Bv(l));
+                __syncthreads();
+                smooth0(l, l == a.nlev - 1 ? a.v1 : a.v0);
+            }
+            for (int l = a.nlev - 2; l >= r; l--) {
+                tail_prolong_add<T, DIM>(a.n[l], a.n[l + 1], A(l + 1, cur[l + 1]), A(l, cur[l]));
+                __syncthreads();
+                sweeps(l, a.v0);
+            }
+        }
+    }
+    {
+        const int n = a.n[0], m = n + 2, N = (DIM == 3) ? n * n * n : n * n;
+        const T *u0 = A(0, cur[0]);
+        for (int p = threadIdx.x; p < N; p += blockDim.x) {
+            const int j = p % n, i = (p / n) % n, k = (DIM == 3) ? p / (n * n) : 0;
+            a.u_out[(long)k * a.ms + (long)i * a.rs + j] = u0[tail_idx<T, DIM>(m, k, i, j)];
+        }
+    }
+}
+
 static thread_local long long *g_tail_stamps = nullptr;
 // profiling aid: the tail kernels launched by this thread deposit (s_memrealtime, s_memtime) at each of their barriers into dev[0 .. 255]
 // and the number of pairs into dev[256] (257 long longs of device memory; null switches it off)
 extern "C" void mgk_debug_tail_stamps(long long *dev) { g_tail_stamps = dev; }
 template <typename T>
 static int tail_cycle(mgk_ctx *c, const mgk_geom *g0, int nlev, const int *n, const double *coef7, const double *dinv, double scale,
-                      int v0, int v1, const T *b, T *u, void *stream, const T *const *ctab = nullptr, const T *const *dtab = nullptr, const double *cscale = nullptr) {
+                      int v0, int v1, const T *b, T *u, void *stream, const T *const *ctab = nullptr, const T *const *dtab = nullptr, const double *cscale = nullptr,
+                      int fmg_nu = 0) {
     if (!c || !g0 || !n || (!coef7 && !ctab) || (!dinv && !dtab) || !b || !u || nlev < 1 || nlev > MGK_TAIL_MAXLEV || v0 < 0 || v1 < 0 ||
         (ctab && (!dtab || g0->dim != 2)))
         return fail(MGK_EINVAL, "mgk_tail_cycle: bad arguments");
@@ -5245,7 +5350,10 @@ static int tail_cycle(mgk_ctx *c, const mgk_geom *g0, int nlev, const int *n, co
     a.total = (int)off;
     a.b_in = b + g0->org; a.u_out = u + g0->org; a.rs = g0->pitch; a.ms = g0->plane;
     a.stamps = g_tail_stamps;
-    if (g0->dim == 3) hipLaunchKernelGGL((k_tail<T, 3>), dim3(1), dim3(1024), 0, S(c, stream), a);
+    if (fmg_nu > 0) {
+        if (g0->dim == 3) hipLaunchKernelGGL((k_tail_fmg<T, 3>), dim3(1), dim3(1024), 0, S(c, stream), a, fmg_nu);
+        else hipLaunchKernelGGL((k_tail_fmg<T, 2>), dim3(1), dim3(1024), 0, S(c, stream), a, fmg_nu);
+    } else if (g0->dim == 3) hipLaunchKernelGGL((k_tail<T, 3>), dim3(1), dim3(1024), 0, S(c, stream), a);
     else hipLaunchKernelGGL((k_tail<T, 2>), dim3(1), dim3(1024), 0, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
@@ -5273,6 +5381,12 @@ extern "C" int mgk_tail_cycle_cs_f64(mgk_ctx *c, const mgk_geom *g0, int nlev, c
     return tail_cycle<double>(c, g0, nlev, n, ctab ? nullptr : coef7, ctab ? nullptr : dinv, scale, v0, v1, b, u, stream, ctab, dtab, &coarse_scale);
 }
 extern "C" int mgk_tail_max_n(int dim) { return dim == 3 ? 15 : 63; }
+// FMG(nu) on the tail levels in one launch (k_tail_fmg): b of the first tail level in, its u after the stage rooted there out
+extern "C" int mgk_tail_fmg_f64(mgk_ctx *c, const mgk_geom *g0, int nlev, const int *n, const double *coef7, const double *dinv,
+                                double scale, int v0, int v1, int nu, const double *b, double *u, void *stream) {
+    if (nu < 1 || nlev < 2 || b == u) return fail(MGK_EINVAL, "mgk_tail_fmg_f64: need nu >= 1, two levels or more, b != u");
+    return tail_cycle<double>(c, g0, nlev, n, coef7, dinv, scale, v0, v1, b, u, stream, nullptr, nullptr, nullptr, nu);
+}
 
 
 // ------------------------------------------------------------------------------------------

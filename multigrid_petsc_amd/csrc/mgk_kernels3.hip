@@ -10,6 +10,8 @@
 //                makes ALL pre-smoothing sweeps of cycle k+1 (:1531); adopted only if a next cycle runs
 //     ZG         from the zero guess: the first sweep is pointwise, u1 = scale * (b * dinv); u is not read: 8 + 8 B (:1536 on a coarse level)
 //     PRO        unew = J(J(J(u + P uc))): prolongation, correction and ALL post-smoothing sweeps (:1540-1542): 25 B
+//     PRO + ZG   unew = J(J(J(0 + P uc))): the FMG interpolation (u not read) and the three pre-smoothing sweeps of the V-cycle that
+//                starts from it: 8 + 2 + 8 = 18 B
 // With these a V(3,3) cycle makes three passes over a level -- (N + S1 S2 S3)(R)(P + S1' S2' S3') = 24 + 18 + 25 = 67 B on the fine
 // level, (J3 from b)(R)(P + 3 sweeps) = 16 + 18 + 25 = 59 B below -- instead of four (99 / 91 B).
 // Structure of k_pj2d / k_rr2d: every WAVE is independent (no LDS, no barrier).  Lane l holds the column pair x0 = 2 (60 tx + l - 2);
@@ -41,6 +43,7 @@ struct J3dArgs {
 template <bool PRO, bool ZG, bool NORM, bool TAB, int YC>
 __global__ void __launch_bounds__(256) k_jacobi3_2d(const J3dArgs a) {
     using VT = V16<double>;
+    constexpr bool ZU = PRO && ZG, ZS = ZG && !PRO;           // ZU: u counts as zero everywhere (FMG interpolation); ZS: pointwise first sweep
     const int lane = threadIdx.x & 63;
     // workgroups are dealt round-robin over the 8 XCDs: give every XCD a CONTIGUOUS range of wave tiles, so that the rows and columns
     // neighbouring tiles share are re-read from the L2 they were first brought into (the grid is padded to a multiple of 8 blocks)
@@ -165,7 +168,7 @@ __global__ void __launch_bounds__(256) k_jacobi3_2d(const J3dArgs a) {
         VT &q0 = QQ[K & 1], &q1 = QQ[(K + 1) & 1];
         VT &b0 = BB[K % 3], &b1 = BB[(K + 1) % 3], &b2 = BB[(K + 2) % 3];
         VT p2;
-        if (ZG) p2 = sweep0(b2, ph(t + 2), kc2);
+        if (ZS) p2 = sweep0(b2, ph(t + 2), kc2);
         else {
             const VT uc = correct(ur, ph(t + 3), cA, cB);
             p2 = REV ? sweep(uc, ub, ua, b2, ph(t + 2), true, kc2) : sweep(ua, ub, uc, b2, ph(t + 2), true, kc2);
@@ -190,12 +193,12 @@ __global__ void __launch_bounds__(256) k_jacobi3_2d(const J3dArgs a) {
         double Cc[NC];
         const int c0 = pA(t0 + 1);                            // first coarse row needed
 #pragma unroll
-        for (int q = 0; q < NU; q++) { if (!ZG) U[q] = ldraw(t0 + 1 + q); B[q] = ldbraw(t0 + 1 + q); }
+        for (int q = 0; q < NU; q++) { U[q] = ZG ? Z : ldraw(t0 + 1 + q); B[q] = ldbraw(t0 + 1 + q); }
 #pragma unroll
         for (int q = 0; q < NC; q++) Cc[q] = ldc(c0 + q);
         // t0 = cy * YC - 4 is even, so the parents of row t0 + k are the coarse rows c0 + (k - 1) / 2 (k odd) or c0 + k / 2 - 1 and
         // c0 + k / 2 (k even) with c0 = t0 / 2: every index below is a compile-time constant once the loop is unrolled
-        if (!ZG) {
+        if (!ZS) {
             UU[0] = correct(U[0], t0 + 1, Cc[0], Cc[0]);
             UU[1] = correct(U[1], t0 + 2, Cc[0], Cc[1]);
         }
@@ -213,16 +216,16 @@ __global__ void __launch_bounds__(256) k_jacobi3_2d(const J3dArgs a) {
             auto ph = [&](int tt) -> int { return REV ? (y0 + y1 - 1 - tt) : tt; };
             VT UR[2] = {Z, Z}, BN[2];                         // the loads a step consumes are requested a step ahead: two sets, roles by phase
             double CA[2] = {0.0, 0.0}, CB[2] = {0.0, 0.0};
-            if (!ZG) {
-                UU[0] = correct(ldraw(ph(t0 + 1)), ph(t0 + 1), ldc(pA(ph(t0 + 1))), ldc(pB(ph(t0 + 1))));
-                UU[1] = correct(ldraw(ph(t0 + 2)), ph(t0 + 2), ldc(pA(ph(t0 + 2))), ldc(pB(ph(t0 + 2))));
-                UR[0] = ldraw(ph(t0 + 3));
+            if (!ZS) {
+                UU[0] = correct(ZU ? Z : ldraw(ph(t0 + 1)), ph(t0 + 1), ldc(pA(ph(t0 + 1))), ldc(pB(ph(t0 + 1))));
+                UU[1] = correct(ZU ? Z : ldraw(ph(t0 + 2)), ph(t0 + 2), ldc(pA(ph(t0 + 2))), ldc(pB(ph(t0 + 2))));
+                UR[0] = ZU ? Z : ldraw(ph(t0 + 3));
                 CA[0] = ldc(pA(ph(t0 + 3))); CB[0] = ldc(pB(ph(t0 + 3)));
             }
             BB[2] = fix(ldbraw(ph(t0 + 2)), ph(t0 + 2));
             BN[0] = ldbraw(ph(t0 + 3));
             auto S = [&](const int K, int t) {
-                if (!ZG) { UR[(K + 1) & 1] = ldraw(ph(t + 4)); CA[(K + 1) & 1] = ldc(pA(ph(t + 4))); CB[(K + 1) & 1] = ldc(pB(ph(t + 4))); }
+                if (!ZS) { UR[(K + 1) & 1] = ZU ? Z : ldraw(ph(t + 4)); CA[(K + 1) & 1] = ldc(pA(ph(t + 4))); CB[(K + 1) & 1] = ldc(pB(ph(t + 4))); }
                 BN[(K + 1) & 1] = ldbraw(ph(t + 4));
                 stepg(revc, K, t, UR[K & 1], CA[K & 1], CB[K & 1], BN[K & 1]);
             };
@@ -330,6 +333,13 @@ extern "C" int mgk_jacobi3_2d_zero_f64(mgk_ctx *c, const mgk_geom *g, const doub
 extern "C" int mgk_prolong_jacobi3_2d_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
                                           const double *ctab, const double *dtab, const double *b, const double *uc, const double *u, double *unew, void *stream) {
     return jacobi3_2d<true, false, false>(c, gf, gc, coef, dinv, scale, ctab, dtab, b, uc, u, unew, stream, nullptr);
+}
+// FMG interpolation (full multigrid), uniform mesh: unew = J(J(J(0 + P uc))) -- the interpolated coarse solution as the new iterate and the
+// three pre-smoothing sweeps of the V-cycle that starts from it, in one pass over b and uc (the old unew is never read).  Any 2-D grid
+extern "C" int mgk_interp_jacobi3_2d_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
+                                         const double *b, const double *uc, double *unew, void *stream) {
+    if (!coef || !uc || unew == uc) return fail(MGK_EINVAL, "mgk_interp_jacobi3_2d_f64: bad arguments");
+    return jacobi3_2d<true, true, false>(c, gf, gc, coef, dinv, scale, nullptr, nullptr, b, uc, nullptr, unew, stream, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -83,6 +83,16 @@ def _lib():
     return L
 
 
+def _fmg_lib(L):
+    """the full-multigrid entry points, bound on first use (a library built without them still serves everything else)"""
+    if not getattr(L, "_mg_fmg_sigs", False):
+        for f in ("mg_solver_fmg", "mg_solver_solve_fmg"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p, C.c_int]
+        L._mg_fmg_sigs = True
+    return L
+
+
 def get_ranges(totaln, procs):
     r = np.zeros(procs + 1, dtype=np.int32)
     _lib().mg_get_ranges(totaln, procs, r.ctypes.data_as(C.c_void_p))
@@ -149,6 +159,16 @@ class Solver:
 
     def cycles(self, n):
         self._chk(self.L.mg_solver_cycles(self.h, n))
+
+    def fmg(self, nu=1):
+        """full multigrid FMG(nu) on the current right-hand side; counts as iteration 1, cycles() continues from its result"""
+        self._chk(_fmg_lib(self.L).mg_solver_fmg(self.h, nu))
+        return self.iterations
+
+    def solve_fmg(self, nu=1):
+        """FMG(nu), then V-cycles under solve()'s stop rule; returns the iteration count (FMG included)"""
+        self._chk(_fmg_lib(self.L).mg_solver_solve_fmg(self.h, nu))
+        return self.iterations
 
     def sync(self):
         self._chk(self.L.mg_solver_sync(self.h))
