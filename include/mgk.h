@@ -266,6 +266,13 @@ int  mgk_tail_fmg_f64(mgk_ctx *ctx, const mgk_geom *g0, int nlev, const int *n, 
 int  mgk_tail_cycle_cs_f64(mgk_ctx *ctx, const mgk_geom *g0, int nlev, const int *n, const double *coef7, const double *dinv,
                            const double *const *ctab, const double *const *dtab, double scale, double coarse_scale, int v0, int v1,
                            const double *b, double *u, void *stream);
+/* ... with KSPCHEBYSHEV (eigenvalue bounds emin < emax) on every level (fp64, 2-D and 3-D; coef7 + dinv or the row tables): every
+ * KSPSolve is the restarted recurrence -- a first step with scale 2/(emax+emin) (taken even when the step count is 0, as PETSc does), then
+ * steps that write p_{k+1} over p_{k-1} in the level's ping-pong pair.  0 <= v0, v1 <= 16.  Bit-identical to mgk_jacobi[_zero]_f64 +
+ * mgk_cheby_f64 launched step by step */
+int  mgk_tail_cycle_cheby_f64(mgk_ctx *ctx, const mgk_geom *g0, int nlev, const int *n, const double *coef7, const double *dinv,
+                              const double *const *ctab, const double *const *dtab, double emin, double emax, int v0, int v1,
+                              const double *b, double *u, void *stream);
 int  mgk_tail_max_n(int dim);
 /* profiling aid: the tail kernels this thread launches deposit (s_memrealtime [100 MHz], s_memtime [shader clock]) pairs at each of their
  * barriers into dev[0 .. 255] and the number of pairs into dev[256] (257 long longs of DEVICE memory; NULL switches it off) */
@@ -471,6 +478,20 @@ int  mgk_jacobi3_2d_zero_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef
 int  mgk_prolong_jacobi3_2d_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
                                 const double *ctab, const double *dtab, const double *b, const double *uc, const double *u, double *unew,
                                 void *stream);
+/* The same four passes with KSPCHEBYSHEV: a whole KSPSolve with max_it = 3 (the recurrence restarts at every KSPSolve, so it is exactly
+ * three steps) in one pass with the bytes of the Jacobi pass.  cheb = {s, c_km1, c_k, c_z of step 2, c_km1, c_k, c_z of step 3}
+ * (mg_cheby_begin / mg_cheby_next, include/mg_cheby_coefs.h) takes the place of scale: stage 1 is the sweep with scale s, stages 2 and 3 evaluate
+ * (c_km1*prev + c_k*cur) + c_z*((b - A cur)*dinv) as mgk_cheby_f64 does, prev being the value the previous stage started from at the
+ * point itself (zero from the zero guess).  Bit-identical to mgk_jacobi[_zero]_f64 + two mgk_cheby_f64 calls */
+int  mgk_cheby3_2d_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef, double dinv, const double *cheb, const double *ctab, const double *dtab,
+                       const double *b, const double *u, double *unew, void *stream);
+int  mgk_cheby3_2d_sumsq_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef, double dinv, const double *cheb, const double *ctab, const double *dtab,
+                             const double *b, const double *u, double *unew, double *sumsq_host, void *stream);
+int  mgk_cheby3_2d_zero_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef, double dinv, const double *cheb, const double *ctab, const double *dtab,
+                            const double *b, double *unew, void *stream);
+int  mgk_prolong_cheby3_2d_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, const double *cheb,
+                               const double *ctab, const double *dtab, const double *b, const double *uc, const double *u, double *unew,
+                               void *stream);
 /* FMG interpolation, 2-D, uniform mesh: unew = J(J(J(0 + P uc))) (the old unew is never read), 18 B per unknown; any 2-D grid */
 int  mgk_interp_jacobi3_2d_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
                                const double *b, const double *uc, double *unew, void *stream);

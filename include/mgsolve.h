@@ -63,7 +63,12 @@ typedef struct mg_config {
                          * second planes of u and of the coarse u arrive in two grouped exchanges hidden behind the interior planes),
                          * mgk_jacobi2_sumsq_mid_slab_f64, the plain fused residual + restriction: every rank moves 91 instead of 99 B per fine
                          * unknown and cycle;
-                         * default (-1): bits 0-5 and 8-14 on */
+                         * bit 15 (32768; KSPCHEBYSHEV, fp64, one rank): the smoothings with exactly three steps of 2-D levels run as ONE three-step
+                         * pass each (mgk_cheby3_2d_*: the passes, swaps and bytes of bit 13's Richardson cycle, coarse-level graph included), and the
+                         * levels that fit in LDS as one kernel per cycle in 2-D and 3-D with any step counts (mgk_tail_cycle_cheby_f64, with bit 9);
+                         * off: every step is a launch of its own.  Like the other bits it exists so that tests can run the unfused path as the
+                         * reference; which path runs is otherwise decided by what the solver sees (dimension, v0, ranks);
+                         * default (-1): bits 0-5 and 8-15 on */
     int overlap;        /* nranks > 1: halo of sweep k on the comm stream while sweep k's interior runs; default on (-1) */
     int graph;          /* replay the launch-bound coarse levels as one captured HIP graph; default on (-1) */
     int pair_min_n;     /* levels with n >= pair_min_n run their sweeps two per pass (fuse bit 5); <=0: default 255 (3-D), 2047 (2-D) */

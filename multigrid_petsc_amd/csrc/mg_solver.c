@@ -261,6 +261,8 @@ static int alloc_fset(mg_solver *s, mg_fset *F, int esz, int all4) {
 }
 
 static int upload(mg_solver *s, const double *h, size_t n, double **d);
+static int cheby_fused(const mg_solver *s);
+static int cheby_steps_by_launch(const mg_solver *s, int l);
 
 /* distributed level: the (nx, ny, 2) field through which the neighbours' second planes of u travel (two-sweep passes) */
 static int alloc_far(mg_solver *s, mg_level *L, int P) {
@@ -313,7 +315,7 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         const int n0 = mg_grid_n(cfg->npts, 0);
         s->cfg.dist_min_n = n0 < 255 ? n0 : 255;
     }
-    if (s->cfg.fuse < 0) s->cfg.fuse = 63 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384;
+    if (s->cfg.fuse < 0) s->cfg.fuse = 63 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768;
     if (s->cfg.pair_min_n <= 0) s->cfg.pair_min_n = (cfg->dim == 3) ? 255 : 2047;   /* where a two-sweep pass beats two sweeps
                                                                                       * (255^3: 0.107 ms against 2 x 0.063) */
     if (s->cfg.mesh) s->cfg.fuse &= ~(16 | 128);   /* row-dependent coefficients (2-D, fp64): the same fused cycle on the row-table forms of the kernels */
@@ -396,29 +398,36 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         }
         if ((rc = alloc_fset(s, &L->f[0], 8, 1))) { mg_solver_destroy(s); return rc; }
         if ((rc = alloc_far(s, L, 0))) { mg_solver_destroy(s); return rc; }
-        if (cfg->ksp_type == MG_KSP_CHEBYSHEV) {
-            void *q = NULL;
-            if ((rc = mgk_malloc(s->ctx, &q, sizeof(double) * (size_t)L->f[0].g.total))) { mg_solver_destroy(s); return mgfail(rc, "mg_solver_create: field"); }
-            L->p2 = (double *)q;
-        }
     }
     /* coarse part for the HIP graph: the first level that is neither distributed nor fed by a distributed one and
      * has at most 2^21 unknowns (3-D n <= 127, 2-D n <= 1023): below that a kernel is shorter than its launch */
     s->lgraph = 0;
-    if (s->cfg.graph && s->cfg.ksp_type == MG_KSP_RICHARDSON) {
+    /* the tail: the first level l >= 1 that is whole on this rank, fed by a whole level... any level qualifies as long as it
+     * and everything below it fit in LDS (n <= mgk_tail_max_n) -- and at least two levels are left, else a tail is no gain */
+    s->ltail = 0;
+    const int cheby_tail = cheby_fused(s) && s->cfg.v[0] >= 0 && s->cfg.v[1] >= 0 && s->cfg.v[0] <= 16 && s->cfg.v[1] <= 16;   /* (the kernel's step table) */
+    if ((s->cfg.fuse & 512) && ((s->cfg.ksp_type == MG_KSP_RICHARDSON && s->cfg.v[0] >= 1) || cheby_tail)) {
+        for (int l = (s->ldist > 0 ? s->ldist : 1); l < s->levels; l++)
+            if (s->L[l].n <= mgk_tail_max_n(cfg->dim)) { s->ltail = l; break; }
+        if (s->ltail && (s->levels - s->ltail < 2 || s->levels - s->ltail > 8)) s->ltail = 0;
+    }
+    if (s->cfg.graph) {
         for (int l = (s->ldist > 0 ? s->ldist + 1 : 1); l < s->levels; l++) {
             double N = pow((double)s->L[l].n, (double)cfg->dim);
             if (N <= 2097152.0) { s->lgraph = l; break; }
         }
         if (s->lgraph && s->levels - s->lgraph < 2) s->lgraph = 0;      /* not worth a graph */
+        /* Chebyshev: smooth_chebyshev rotates three buffers (u, tmp, p2), so a level that runs it has other pointers in every cycle and a
+         * replay would use stale ones (the re-record check watches only the level that feeds the graph): a graph only if every level in
+         * it, and the one that feeds it, is inside the tail kernel or on the three-step passes (one swap per pass, as Richardson) */
+        for (int l = s->lgraph ? s->lgraph - 1 : s->levels; s->cfg.ksp_type == MG_KSP_CHEBYSHEV && l < s->levels; l++)
+            if (cheby_steps_by_launch(s, l)) { s->lgraph = 0; break; }
     }
-    /* the tail: the first level l >= 1 that is whole on this rank, fed by a whole level... any level qualifies as long as it
-     * and everything below it fit in LDS (n <= mgk_tail_max_n) -- and at least two levels are left, else a tail is no gain */
-    s->ltail = 0;
-    if ((s->cfg.fuse & 512) && s->cfg.ksp_type == MG_KSP_RICHARDSON && s->cfg.v[0] >= 1) {
-        for (int l = (s->ldist > 0 ? s->ldist : 1); l < s->levels; l++)
-            if (s->L[l].n <= mgk_tail_max_n(cfg->dim)) { s->ltail = l; break; }
-        if (s->ltail && (s->levels - s->ltail < 2 || s->levels - s->ltail > 8)) s->ltail = 0;
+    for (int l = 0; l < s->levels && cfg->ksp_type == MG_KSP_CHEBYSHEV; l++) {
+        if (!cheby_steps_by_launch(s, l)) continue;                    /* the third vector of the recurrence: only where steps are launched one by one */
+        void *q = NULL;
+        if ((rc = mgk_malloc(s->ctx, &q, sizeof(double) * (size_t)s->L[l].f[0].g.total))) { mg_solver_destroy(s); return mgfail(rc, "mg_solver_create: field"); }
+        s->L[l].p2 = (double *)q;
     }
     s->rnorm_cap = (cfg->maxiter > 0 ? cfg->maxiter : 0) + 1;
     s->rnorm = (double *)calloc((size_t)s->rnorm_cap, sizeof(double));
@@ -668,8 +677,9 @@ static int smooth_chebyshev(mg_solver *s, int l, int maxit) {
     mg_level *L = &s->L[l];
     mg_fset *F = &L->f[0];
     const size_t bytes = sizeof(double) * (size_t)F->g.total;
-    double scale = 2.0 / (s->cfg.emax + s->cfg.emin), alpha = 1.0 - scale * s->cfg.emin, Gamma = 1.0;
-    double mu = 1.0 / alpha, omegaprod = 2.0 / alpha, ckm1 = 1.0, ck = mu, ckp1;
+    mg_cheby_rec rec;                                              /* the factors of the recurrence: mg_cheby_coefs.h, shared with the fused passes */
+    mg_cheby_begin(&rec, s->cfg.emin, s->cfg.emax);
+    const double scale = rec.scale;
     double *pkm1 = (double *)F->u, *pk = (double *)F->tmp, *pkp1 = L->p2;
     const int mesh = s->cfg.mesh != 0;                              /* -mesh 1/2: the same steps on the level's row tables (2-D, one rank) */
     /* the recurrence takes its first step BEFORE its loop (PETSc's cheby.c; oracle/mgo.c: smooth, mgo_chebyshev_csr): with max_it = 0 the
@@ -685,15 +695,14 @@ static int smooth_chebyshev(mg_solver *s, int l, int maxit) {
         else CHK(mgk_jacobi_f64(s->ctx, &F->g, L->coef, L->dinv, scale, (const double *)F->b, pkm1, pk, NULL));
     }
     for (int it = 1; it < maxit; it++) {
-        ckp1 = 2.0 * mu * ck - ckm1;
-        double omega = omegaprod * ck / ckp1;
+        double c3[3];                                               /* 1 - omega, omega, omega * Gamma * scale */
+        mg_cheby_next(&rec, c3);
         CHK(halo(s, 0, L, pk));
-        if (mesh) CHK(mgk_cheby_rowcoef_f64(s->ctx, &F->g, L->ctab, L->dtab, 1.0 - omega, omega, omega * Gamma * scale,
+        if (mesh) CHK(mgk_cheby_rowcoef_f64(s->ctx, &F->g, L->ctab, L->dtab, c3[0], c3[1], c3[2],
                                             (const double *)F->b, pk, pkm1, pkp1, NULL));
-        else CHK(mgk_cheby_f64(s->ctx, &F->g, L->coef, L->dinv, 1.0 - omega, omega, omega * Gamma * scale,
+        else CHK(mgk_cheby_f64(s->ctx, &F->g, L->coef, L->dinv, c3[0], c3[1], c3[2],
                           (const double *)F->b, pk, pkm1, pkp1, NULL));
         double *t = pkm1; pkm1 = pk; pk = pkp1; pkp1 = t;
-        ckm1 = ck; ck = ckp1;
     }
     F->u = pk; F->tmp = pkm1; L->p2 = pkp1;
     F->u_ghost_ok = 0; F->u_ghost_pending = 0;
@@ -730,8 +739,25 @@ static int srr_ok(const mg_solver *s, int P, int l) {
  * (mgk_jacobi3_2d_*): a KSPSolve of >= 3 sweeps from the zero guess starts with one pass over b (16 B), the post-smoothing is ONE pass with
  * the prolongation (25 B), and the norm that closes a cycle makes all three pre-smoothing sweeps of the next one (24 B): with the fused
  * residual + restriction (18 B) a V(3,3) cycle makes three passes over a level, 67 B on the fine level and 59 B below, instead of four. */
+/* fuse bit 15 (KSPCHEBYSHEV; fp64, one rank): PETSc restarts the recurrence at every KSPSolve, so a smoothing with max_it = 3 is exactly three
+ * steps, and the three-sweep pass makes them from registers (the Chebyshev form of the kernel, reached through mg_cheby.c): the same passes,
+ * swaps and bytes as the Richardson cycle.  Exactly three: a fourth step would need the second one, which is never stored.  The levels that
+ * fit in LDS run in the Chebyshev form of the tail kernel with any step counts, in 2-D and 3-D (mg_cheby_tail).  mg_cheby.c is absent
+ * from the builds that link this file against a stand-in of the kernel ABI: the references are weak, and without it everything below
+ * runs step by step as before */
+static int cheby_fused(const mg_solver *s) {
+    return s->cfg.ksp_type == MG_KSP_CHEBYSHEV && (s->cfg.fuse & 32768) && mg_cheby_pass && mg_cheby_tail &&
+           s->cfg.precision == MG_PREC_FP64 && s->cfg.nranks == 1;
+}
 static int j3_2d_ok(const mg_solver *s, int P, int l, int maxit) {
-    return (s->cfg.fuse & 8192) && s->cfg.dim == 2 && P == 0 && s->cfg.ksp_type == MG_KSP_RICHARDSON && maxit >= 3 && !s->L[l].distributed;
+    if (!(s->cfg.fuse & 8192) || s->cfg.dim != 2 || P != 0 || s->L[l].distributed) return 0;
+    if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV) return maxit == 3 && cheby_fused(s);
+    return maxit >= 3;
+}
+/* Chebyshev: does level l ever run smooth_chebyshev (which rotates u, tmp and p2)?  Not inside the tail kernel, not on the three-step passes */
+static int cheby_steps_by_launch(const mg_solver *s, int l) {
+    if (s->ltail && l >= s->ltail) return 0;
+    return !j3_2d_ok(s, 0, l, (l == s->levels - 1 && s->levels > 1) ? s->cfg.v[1] : s->cfg.v[0]);
 }
 static int triple_ok(const mg_solver *s, int P, int l, int maxit) {
     const mg_level *L = &s->L[l];
@@ -743,7 +769,7 @@ static int triple_ok(const mg_solver *s, int P, int l, int maxit) {
 
 /* pre: pre-smoothing, a restriction from this level follows (src/solver.c:1531 / :1536 before :1534 of the next level) */
 static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
-    if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV) return smooth_chebyshev(s, l, maxit);
+    if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV && !j3_2d_ok(s, P, l, maxit)) return smooth_chebyshev(s, l, maxit);
     mg_level *L = &s->L[l];
     mg_fset *F = &L->f[P];
     const mg_ops *O = &OPS[P];
@@ -782,7 +808,8 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
              * speculative sweeps to adopt).  The result goes to tmp and is swapped in: ONE swap in every case (zero guess, plain, adopted
              * norm pass above), like the one pass of the post-smoothing (prolong_smooth) -- the same even count in every cycle, so the
              * pointers the coarse-level graph recorded stay valid */
-            if (!F->guess_nonzero)
+            if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV) CHK(mg_cheby_pass(s, l, F->guess_nonzero ? MG_CHEBY_PLAIN : MG_CHEBY_ZERO, NULL));
+            else if (!F->guess_nonzero)
                 CHK(mgk_jacobi3_2d_zero_f64(s->ctx, &F->g, mesh ? NULL : L->coef, mesh ? 1.0 : L->dinv, s->cfg.scale, mesh ? L->ctab : NULL,
                                             mesh ? L->dtab : NULL, (const double *)F->b, (double *)F->tmp, NULL));
             else
@@ -1019,13 +1046,15 @@ static int prolong_smooth(mg_solver *s, int P, int l) {
     mg_fset *F = &Lf->f[P], *Cq = &Lc->f[P];
     const mg_ops *O = &OPS[P];
     const int v0 = s->cfg.v[0];
-    if (!(s->cfg.fuse & 2) || s->cfg.ksp_type != MG_KSP_RICHARDSON || v0 < 1) {
+    if (!(s->cfg.fuse & 2) || (s->cfg.ksp_type != MG_KSP_RICHARDSON && !j3_2d_ok(s, P, l, v0)) || v0 < 1) {
         CHK(prolong_from(s, P, l));
         return smooth(s, P, l, v0, 0);
     }
     if (j3_2d_ok(s, P, l, v0)) {
         /* 2-D: the prolongation, the correction and the first THREE post-smoothing sweeps in one pass */
         const int mesh = s->cfg.mesh != 0;
+        if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV) CHK(mg_cheby_pass(s, l, MG_CHEBY_PROLONG, NULL));
+        else
         CHK(mgk_prolong_jacobi3_2d_f64(s->ctx, &F->g, &Cq->g, mesh ? NULL : Lf->coef, mesh ? 1.0 : Lf->dinv, s->cfg.scale, mesh ? Lf->ctab : NULL,
                                        mesh ? Lf->dtab : NULL, (const double *)F->b, (const double *)Cq->u, (const double *)F->u, (double *)F->tmp, NULL));
         swap_ptr(&F->u, &F->tmp);
@@ -1120,6 +1149,11 @@ static int tail(mg_solver *s, int P) {
         for (int e = 0; e < 7; e++) k7[7 * q + e] = L->coef[e];
     }
     mg_fset *F = &s->L[lt].f[P];
+    if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV) {
+        CHK(mg_cheby_tail(s));
+        F->jz_ready = 0;
+        return 0;
+    }
     if (s->cfg.mesh) {
         const double *ct[8], *dt[8];
         for (int q = 0; q < nl; q++) { ct[q] = s->L[lt + q].ctab; dt[q] = s->L[lt + q].dtab; }
@@ -1393,7 +1427,8 @@ static int vcycle_once(mg_solver *s) {
     } else {
         CHK(cycle_body(s, 0, s->iter == 0));
         /* :1545-1546  r0 = b0 - A0 u0 ; ||r0|| */
-        const int jnorm = (s->cfg.fuse & 8) && (s->cfg.fuse & 1) && s->cfg.ksp_type == MG_KSP_RICHARDSON && s->cfg.v[0] >= 1 && !s->last_cycle;
+        const int jnorm = (s->cfg.fuse & 8) && (s->cfg.fuse & 1) && (s->cfg.ksp_type == MG_KSP_RICHARDSON || j3_2d_ok(s, 0, 0, s->cfg.v[0])) &&
+                          s->cfg.v[0] >= 1 && !s->last_cycle;
         if (s->sweep_owed && L->distributed) {
             /* ... on a z-slab: the planes 2 .. nz-3 while the grouped exchange (u's ghosts, the far planes; b's are valid) travels, one reduction
              * over the block partials of the three launches */
@@ -1487,7 +1522,8 @@ static int vcycle_once(mg_solver *s) {
                 s->prof_kind = 1;
                 void *t = prof_begin(s, 0);
                 s->prof_kind = 0;
-                int rc2 = mgk_jacobi3_2d_sumsq_f64(s->ctx, &F->g, mesh ? NULL : L->coef, mesh ? 1.0 : L->dinv, s->cfg.scale, mesh ? L->ctab : NULL,
+                int rc2 = s->cfg.ksp_type == MG_KSP_CHEBYSHEV ? mg_cheby_pass(s, 0, MG_CHEBY_NORM, &ss) :
+                          mgk_jacobi3_2d_sumsq_f64(s->ctx, &F->g, mesh ? NULL : L->coef, mesh ? 1.0 : L->dinv, s->cfg.scale, mesh ? L->ctab : NULL,
                                                    mesh ? L->dtab : NULL, (const double *)F->b, (const double *)F->u, (double *)F->tmp, &ss, NULL);
                 prof_end(s, t);
                 CHK(rc2);

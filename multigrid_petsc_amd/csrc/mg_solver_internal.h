@@ -7,6 +7,7 @@
 #define MG_SOLVER_INTERNAL_H
 #include "mgsolve.h"
 #include "mg_comm.h"
+#include "mg_cheby_coefs.h"
 
 #define MG_MAX_LEVELS 32
 #define MG_MAX_TIMERS 4096
@@ -78,6 +79,15 @@ struct mg_solver {
     int prof_kind;          /* kind of the next timer: 0 plain sweep, 1 two sweeps in one pass */
     int ntimers_created;
 };
+
+/* KSPCHEBYSHEV on the fused cycle (fuse bit 15): mg_cheby.c holds the only calls of the mgk_cheby3_2d_* / mgk_tail_cycle_cheby_f64 kernels.
+ * mg_solver.c reaches it through these WEAK references and tests them for NULL: a build without mg_cheby.c (the host tests link mg_solver.c
+ * against a stand-in of the kernel ABI that knows none of those kernels) needs no new symbol and runs Chebyshev step by step as before */
+enum { MG_CHEBY_ZERO = 0, MG_CHEBY_PLAIN = 1, MG_CHEBY_PROLONG = 2, MG_CHEBY_NORM = 3 };
+/* KSPSolve(max_it = 3) on level l in one pass, u (from zero / as it is / + P u_{l+1}) -> tmp; NORM: and *sumsq = ||b - A u||^2 of the input.
+ * The caller swaps u / tmp */
+extern int mg_cheby_pass(mg_solver *s, int l, int kind, double *sumsq) __attribute__((weak));
+extern int mg_cheby_tail(mg_solver *s) __attribute__((weak));      /* the levels ltail .. L-1 of one cycle in one kernel */
 
 /* the steps of mg_solver.c, for mg_fmg.c (fp64, one rank) */
 int    mgi_fail(int code, const char *what);            /* records the message for mg_last_error(), returns code */

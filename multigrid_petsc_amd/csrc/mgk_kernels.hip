@@ -15,6 +15,8 @@
 //   k_prolong*         MatMult(pro[l],u,rv)+VecAXPY            src/solver.c:1540-1541 (matrix :1131-1152)
 //   k_sumsq            VecNorm(NORM_2)                         src/solver.c:1512,1518,1546
 #include "mgk_dev.hpp"
+#include <type_traits>
+#include "mg_cheby_coefs.h"
 
 thread_local char g_err[512] = "ok";
 int fail(int code, const char *what) {
@@ -5239,6 +5241,107 @@ __global__ void __launch_bounds__(1024) k_tail(const TailArgs<T> a) {
     if (a.stamps && threadIdx.x == 0) a.stamps[256] = nstamp;
 }
 
+// The tail with KSPCHEBYSHEV on every level (mgk_tail_cycle_cheby_f64; fp64): every KSPSolve is the restarted three-term recurrence of
+// k_stencil<MODE_CHEBY> / smooth_chebyshev (mg_solver.c).  Its first step is a sweep with scale s = 2 / (emax + emin) (mode 2 from the
+// zero guess, mode 0 otherwise; taken even when the step count is 0, as PETSc's cheby.c does); a further step reads p_k from one array of
+// the level's ping-pong pair and p_{k-1} -- at the point itself only -- from the other, and writes p_{k+1} over it: two arrays per level
+// suffice.  From the zero guess p_0 is the partner array, all zeros until the level's first solve of this launch.
+#define MGK_TAIL_CHEB_MAXIT 16
+struct TailChebArgs {
+    TailArgs<double> t;
+    double s;                                   // scale of the first step
+    double c[MGK_TAIL_CHEB_MAXIT - 1][3];       // {1 - omega, omega, omega * Gamma * s} of the steps 2, 3, ...
+};
+// out = (c_km1 * out + c_k * pk) + c_z * ((b - A pk) * dinv): out holds p_{k-1} and receives p_{k+1}
+template <int DIM>
+__device__ void tail_cheby_step(int n, const double *cf_, double dinv_, double ckm1, double ck, double cz, const double *pk, const double *b, double *out,
+                                const double *ctab, const double *dtab) {
+    const int m = n + 2, sk = m * m;
+    tail_points<DIM>(n, [&](int k, int i, int j) {
+        const int q = tail_idx<double, DIM>(m, k, i, j);
+        const double *cf = (DIM == 2 && ctab) ? ctab + 5 * i : cf_;
+        const double dinv = (DIM == 2 && dtab) ? dtab[i] : dinv_;
+        double t;
+        if (DIM == 3) {
+            t = cf[0] * pk[q - sk];
+            t = t + cf[1] * pk[q - m];
+            t = t + cf[2] * pk[q - 1];
+            t = t + cf[3] * pk[q];
+            t = t + cf[4] * pk[q + 1];
+            t = t + cf[5] * pk[q + m];
+            t = t + cf[6] * pk[q + sk];
+        } else {
+            t = cf[0] * pk[q - m];
+            t = t + cf[1] * pk[q - 1];
+            t = t + cf[2] * pk[q];
+            t = t + cf[3] * pk[q + 1];
+            t = t + cf[4] * pk[q + m];
+        }
+        const double res = b[q] - t;
+        const double zz = res * dinv;
+        out[q] = (ckm1 * out[q] + ck * pk[q]) + cz * zz;
+    });
+}
+template <int DIM>
+__global__ void __launch_bounds__(1024) k_tail_cheby(const TailChebArgs ca) {
+    using T = double;
+    const TailArgs<double> &a = ca.t;
+    __shared__ __attribute__((aligned(16))) unsigned char raw[MGK_TAIL_LDS_BYTES];
+    T *lds = reinterpret_cast<T *>(raw);
+    for (int q = threadIdx.x; q < a.total; q += blockDim.x) lds[q] = (T)0;        // ghost rings stay 0 (homogeneous Dirichlet)
+    __syncthreads();
+    int cur[MGK_TAIL_MAXLEV];                     // which of A0 / A1 holds u of the level
+    auto A = [&](int l, int which) -> T * { const int m = a.n[l] + 2; const int sz = (DIM == 3) ? m * m * m : m * m; return lds + a.off[l] + which * sz; };
+    auto Bv = [&](int l) -> T * { return A(l, 2); };
+    {   // b of the first tail level from global memory
+        const int n = a.n[0], m = n + 2, N = (DIM == 3) ? n * n * n : n * n;
+        T *b0 = Bv(0);
+        for (int p = threadIdx.x; p < N; p += blockDim.x) {
+            const int j = p % n, i = (p / n) % n, k = (DIM == 3) ? p / (n * n) : 0;
+            b0[tail_idx<T, DIM>(m, k, i, j)] = a.b_in[(long)k * a.ms + (long)i * a.rs + j];
+        }
+    }
+    __syncthreads();
+    // KSPSolve with max_it = steps: from the zero guess (the level's two arrays are still all zeros: A1 is p_0) or from the guess in A(l, cur[l])
+    auto solve = [&](int l, int steps, bool zero) {
+        if (zero) {
+            cur[l] = 0;
+            tail_stencil<T, DIM>(2, a.n[l], a.coef[l], a.dinv[l], ca.s, A(l, 0), Bv(l), A(l, 0), a.ctab[l], a.dtab[l]);
+        } else {
+            tail_stencil<T, DIM>(0, a.n[l], a.coef[l], a.dinv[l], ca.s, A(l, cur[l]), Bv(l), A(l, cur[l] ^ 1), a.ctab[l], a.dtab[l]);
+            cur[l] ^= 1;
+        }
+        __syncthreads();
+        for (int it = 1; it < steps; it++) {
+            tail_cheby_step<DIM>(a.n[l], a.coef[l], a.dinv[l], ca.c[it - 1][0], ca.c[it - 1][1], ca.c[it - 1][2], A(l, cur[l]), Bv(l), A(l, cur[l] ^ 1),
+                                 a.ctab[l], a.dtab[l]);
+            __syncthreads();
+            cur[l] ^= 1;
+        }
+    };
+    solve(0, a.nlev == 1 ? a.v1 : a.v0, true);
+    for (int l = 1; l < a.nlev; l++) {            // :1534-1537
+        tail_stencil<T, DIM>(1, a.n[l - 1], a.coef[l - 1], a.dinv[l - 1], ca.s, A(l - 1, cur[l - 1]), Bv(l - 1), A(l - 1, cur[l - 1] ^ 1), a.ctab[l - 1], a.dtab[l - 1]);
+        __syncthreads();
+        tail_restrict<T, DIM>(a.n[l - 1], a.n[l], A(l - 1, cur[l - 1] ^ 1), Bv(l));
+        __syncthreads();
+        solve(l, l == a.nlev - 1 ? a.v1 : a.v0, true);
+    }
+    for (int l = a.nlev - 2; l >= 0; l--) {       // :1540-1542
+        tail_prolong_add<T, DIM>(a.n[l], a.n[l + 1], A(l + 1, cur[l + 1]), A(l, cur[l]));
+        __syncthreads();
+        solve(l, a.v0, false);
+    }
+    {
+        const int n = a.n[0], m = n + 2, N = (DIM == 3) ? n * n * n : n * n;
+        const T *u0 = A(0, cur[0]);
+        for (int p = threadIdx.x; p < N; p += blockDim.x) {
+            const int j = p % n, i = (p / n) % n, k = (DIM == 3) ? p / (n * n) : 0;
+            a.u_out[(long)k * a.ms + (long)i * a.rs + j] = u0[tail_idx<T, DIM>(m, k, i, j)];
+        }
+    }
+}
+
 // Full multigrid on the tail levels (mgk_tail_fmg_f64), one launch: b of the first tail level comes in, the FMG restriction chain
 // b_l = R b_{l-1} runs down, the coarsest level gets v1 sweeps from the zero guess, and for every root r = nlev-2 .. 0: u_r = 0 + P u_{r+1}
 // (level r's arrays are untouched until its stage: A0 is still all zeros), then nu V-cycles on the levels r .. nlev-1 -- v0 sweeps on r from
@@ -5328,7 +5431,7 @@ extern "C" void mgk_debug_tail_stamps(long long *dev) { g_tail_stamps = dev; }
 template <typename T>
 static int tail_cycle(mgk_ctx *c, const mgk_geom *g0, int nlev, const int *n, const double *coef7, const double *dinv, double scale,
                       int v0, int v1, const T *b, T *u, void *stream, const T *const *ctab = nullptr, const T *const *dtab = nullptr, const double *cscale = nullptr,
-                      int fmg_nu = 0) {
+                      int fmg_nu = 0, const double *cheb_eig = nullptr) {
     if (!c || !g0 || !n || (!coef7 && !ctab) || (!dinv && !dtab) || !b || !u || nlev < 1 || nlev > MGK_TAIL_MAXLEV || v0 < 0 || v1 < 0 ||
         (ctab && (!dtab || g0->dim != 2)))
         return fail(MGK_EINVAL, "mgk_tail_cycle: bad arguments");
@@ -5350,6 +5453,24 @@ static int tail_cycle(mgk_ctx *c, const mgk_geom *g0, int nlev, const int *n, co
     a.total = (int)off;
     a.b_in = b + g0->org; a.u_out = u + g0->org; a.rs = g0->pitch; a.ms = g0->plane;
     a.stamps = g_tail_stamps;
+    if constexpr (std::is_same<T, double>::value) {
+        if (cheb_eig) {
+            // Chebyshev: the step factors of the longest solve, evaluated here with the expressions of smooth_chebyshev (mg_cheby_begin / _next)
+            const int steps = v0 > v1 ? v0 : v1;
+            if (steps > MGK_TAIL_CHEB_MAXIT || !(cheb_eig[1] > cheb_eig[0] && cheb_eig[0] > 0.0))
+                return fail(MGK_EINVAL, "mgk_tail_cycle_cheby_f64: need 0 < emin < emax and at most 16 steps per solve");
+            TailChebArgs ca; memset(&ca, 0, sizeof(ca));
+            ca.t = a; ca.t.stamps = nullptr;
+            mg_cheby_rec rec;
+            mg_cheby_begin(&rec, cheb_eig[0], cheb_eig[1]);
+            ca.s = rec.scale;
+            for (int it = 1; it < steps; it++) mg_cheby_next(&rec, ca.c[it - 1]);
+            if (g0->dim == 3) hipLaunchKernelGGL((k_tail_cheby<3>), dim3(1), dim3(1024), 0, S(c, stream), ca);
+            else hipLaunchKernelGGL((k_tail_cheby<2>), dim3(1), dim3(1024), 0, S(c, stream), ca);
+            HIPCHK(hipGetLastError());
+            return 0;
+        }
+    }
     if (fmg_nu > 0) {
         if (g0->dim == 3) hipLaunchKernelGGL((k_tail_fmg<T, 3>), dim3(1), dim3(1024), 0, S(c, stream), a, fmg_nu);
         else hipLaunchKernelGGL((k_tail_fmg<T, 2>), dim3(1), dim3(1024), 0, S(c, stream), a, fmg_nu);
@@ -5379,6 +5500,15 @@ extern "C" int mgk_tail_cycle_cs_f64(mgk_ctx *c, const mgk_geom *g0, int nlev, c
                                      const double *b, double *u, void *stream) {
     if ((ctab == nullptr) != (dtab == nullptr)) return fail(MGK_EINVAL, "mgk_tail_cycle_cs_f64: ctab and dtab go together");
     return tail_cycle<double>(c, g0, nlev, n, ctab ? nullptr : coef7, ctab ? nullptr : dinv, scale, v0, v1, b, u, stream, ctab, dtab, &coarse_scale);
+}
+// ... with KSPCHEBYSHEV (eigenvalue bounds emin, emax) as every level's solver: k_tail_cheby.  2-D and 3-D; either coef7 + dinv or the
+// row tables (2-D); any v0, v1 in 0 .. 16
+extern "C" int mgk_tail_cycle_cheby_f64(mgk_ctx *c, const mgk_geom *g0, int nlev, const int *n, const double *coef7, const double *dinv,
+                                        const double *const *ctab, const double *const *dtab, double emin, double emax, int v0, int v1,
+                                        const double *b, double *u, void *stream) {
+    if ((ctab == nullptr) != (dtab == nullptr)) return fail(MGK_EINVAL, "mgk_tail_cycle_cheby_f64: ctab and dtab go together");
+    const double eig[2] = {emin, emax};
+    return tail_cycle<double>(c, g0, nlev, n, ctab ? nullptr : coef7, ctab ? nullptr : dinv, 1.0, v0, v1, b, u, stream, ctab, dtab, nullptr, 0, eig);
 }
 extern "C" int mgk_tail_max_n(int dim) { return dim == 3 ? 15 : 63; }
 // FMG(nu) on the tail levels in one launch (k_tail_fmg): b of the first tail level in, its u after the stage rooted there out

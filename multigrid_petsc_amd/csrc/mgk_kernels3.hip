@@ -32,6 +32,7 @@ struct J3dArgs {
     long rs, crs;
     int ntx, yc, nwaves, xcd, bous, plainst;
     double a0, a2, a3, a4, a6, dinv, scale;
+    double ch[6];                   // CHEB: {c_km1, c_k, c_z} of the second and of the third stage (scale is s of the first)
     const double *ctab, *dtab;
     double *partials;               // NORM: one partial of || b - A u ||^2 per wave
     double *rout;                   // NORM, optional: b - A u of the input field is also STORED (the drop-in's KSPBuildResidual + VecNorm)
@@ -40,7 +41,12 @@ struct J3dArgs {
 // YC > 0 (even): a chunk of exactly YC rows, EVERY load of the chunk issued before the first sweep and the marching loop fully unrolled
 // (the levels that fit the caches, 127^2 .. 1023^2: they are short of waves, not of bandwidth -- a wave that waits for one row per
 // step spends 0.7 us per step; with all its rows requested at once it pays the latency once).
-template <bool PRO, bool ZG, bool NORM, bool TAB, int YC>
+// CHEB: the three stages are the three steps of a restarted Chebyshev recurrence (KSPCHEBYSHEV with max_it = 3) instead of three
+// Richardson sweeps: stage 1 is the sweep with scale s = 2 / (emax + emin); stages 2 and 3 are (c_km1 * prev + c_k * cur) + c_z * zz, the
+// expression of k_stencil<MODE_CHEBY>, where prev is the iterate BEFORE cur at the point itself -- the corrected u row the first stage read
+// (zero from the zero guess) and the first-stage row the second one read: both are still in the rings when they are needed, so no halo
+// widens and nothing more is loaded.  The seven factors are launch constants (scalar registers).
+template <bool PRO, bool ZG, bool NORM, bool TAB, int YC, bool CHEB = false>
 __global__ void __launch_bounds__(256) k_jacobi3_2d(const J3dArgs a) {
     using VT = V16<double>;
     constexpr bool ZU = PRO && ZG, ZS = ZG && !PRO;           // ZU: u counts as zero everywhere (FMG interpolation); ZS: pointwise first sweep
@@ -116,8 +122,9 @@ __global__ void __launch_bounds__(256) k_jacobi3_2d(const J3dArgs a) {
                  k6 = TAB ? (kk).k6 : a.a6, kd = TAB ? (kk).kd : a.dinv;
     // one sweep of row y from the rows lo / c / hi of the previous iterate
     double nacc = 0.0;
-    auto sweep = [&](const VT &lo, const VT &c, const VT &hi, const VT &bb, int y, bool norm, const K6 &kk) -> VT {
+    auto sweep = [&](const VT &lo, const VT &c, const VT &hi, const VT &bb, int y, bool norm, const K6 &kk, const int stage = 0, const VT &prev = VT()) -> VT {
         J3_COEFS(kk)
+        const double ckm1 = CHEB ? a.ch[stage == 2 ? 3 : 0] : 0.0, ck = CHEB ? a.ch[stage == 2 ? 4 : 1] : 0.0, cz = CHEB ? a.ch[stage == 2 ? 5 : 2] : 0.0;
         const double Wv = lane_up<true>(c.v[1]), Ev = lane_dn<true>(c.v[0]);
         VT o, rr;
 #pragma unroll
@@ -131,7 +138,8 @@ __global__ void __launch_bounds__(256) k_jacobi3_2d(const J3dArgs a) {
             s = s + k6 * hi.v[e];
             const double res = bb.v[e] - s;
             const double zz = res * kd;
-            o.v[e] = c.v[e] + a.scale * zz;
+            if (CHEB && stage > 0) o.v[e] = (ckm1 * prev.v[e] + ck * c.v[e]) + cz * zz;
+            else o.v[e] = c.v[e] + a.scale * zz;
             rr.v[e] = (lastvec && e == 1) ? 0.0 : res;
             if (NORM && norm) nacc += (store && y >= y0 && y < y1 && !(lastvec && e == 1)) ? res * res : 0.0;     // the points this wave owns
         }
@@ -167,21 +175,25 @@ __global__ void __launch_bounds__(256) k_jacobi3_2d(const J3dArgs a) {
         VT &p0 = PP[K & 1], &p1 = PP[(K + 1) & 1];
         VT &q0 = QQ[K & 1], &q1 = QQ[(K + 1) & 1];
         VT &b0 = BB[K % 3], &b1 = BB[(K + 1) % 3], &b2 = BB[(K + 2) % 3];
-        VT p2;
+        VT p2, ucc = Z;
         if (ZS) p2 = sweep0(b2, ph(t + 2), kc2);
         else {
             const VT uc = correct(ur, ph(t + 3), cA, cB);
             p2 = REV ? sweep(uc, ub, ua, b2, ph(t + 2), true, kc2) : sweep(ua, ub, uc, b2, ph(t + 2), true, kc2);
-            ua = uc;                                          // (the next phase's ub)
+            if (!CHEB) ua = uc;                               // (the next phase's ub)
+            else ucc = uc;
         }
         if (t >= y0 - 2) {                                    // wave-uniform
-            const VT q2 = REV ? sweep(p2, p1, p0, b1, ph(t + 1), false, kc1) : sweep(p0, p1, p2, b1, ph(t + 1), false, kc1);
+            // CHEB: prev of the second stage is the iterate the first stage started from on row t+1 (ua; zero from the zero guess), prev of
+            // the third stage the first-stage row t (p0)
+            const VT q2 = REV ? sweep(p2, p1, p0, b1, ph(t + 1), false, kc1, 1, ZS ? Z : ua) : sweep(p0, p1, p2, b1, ph(t + 1), false, kc1, 1, ZS ? Z : ua);
             if (t >= y0 && t < y1) {
-                const VT o = REV ? sweep(q2, q1, q0, b0, ph(t), false, kc0) : sweep(q0, q1, q2, b0, ph(t), false, kc0);
+                const VT o = REV ? sweep(q2, q1, q0, b0, ph(t), false, kc0, 2, p0) : sweep(q0, q1, q2, b0, ph(t), false, kc0, 2, p0);
                 if (store) stv_policy(op_ + (long)ph(t) * a.rs, o, nts);
             }
             q0 = q2;                                          // (the next phase's q1; before the first second sweep both are zero)
         }
+        if (CHEB && !ZS) ua = ucc;                           // (the next phase's ub: after the second stage has read row t+1)
         p0 = p2;
         b0 = fix(bnext, ph(t + 3));                           // (the next phase's b2)
     };
@@ -246,9 +258,11 @@ __global__ void __launch_bounds__(256) k_jacobi3_2d(const J3dArgs a) {
 #undef J3_COEFS
 }
 // shapes: any 2-D grid (nx odd, as everywhere)
-template <bool PRO, bool ZG, bool NORM>
+template <bool PRO, bool ZG, bool NORM, bool CHEB = false>
 static int jacobi3_2d(mgk_ctx *c, const mgk_geom *g, const mgk_geom *gc, const double *coef, double dinv, double scale, const double *ctab, const double *dtab,
-                      const double *b, const double *uc, const double *u, double *unew, void *stream, int *norm_parts, double *rout = nullptr) {
+                      const double *b, const double *uc, const double *u, double *unew, void *stream, int *norm_parts, double *rout = nullptr,
+                      const double *cheb = nullptr) {
+    if (CHEB && !cheb) return fail(MGK_EINVAL, "mgk_cheby3_2d: bad arguments (no coefficients)");
     if (!c || !g || g->dim != 2 || (!coef && !ctab) || (ctab && !dtab) || !b || !unew || (!ZG && (!u || u == unew)) || b == unew)
         return fail(MGK_EINVAL, "mgk_jacobi3_2d: bad arguments (2-D)");
     J3dArgs a; memset(&a, 0, sizeof(a));
@@ -259,7 +273,8 @@ static int jacobi3_2d(mgk_ctx *c, const mgk_geom *g, const mgk_geom *gc, const d
         a.uc = uc + gc->org; a.nxc = gc->nx; a.nyc = gc->ny; a.crs = gc->pitch;
     }
     if (coef) { a.a0 = coef[0]; a.a2 = coef[1]; a.a3 = coef[2]; a.a4 = coef[3]; a.a6 = coef[4]; }
-    a.dinv = dinv; a.scale = scale; a.ctab = ctab; a.dtab = dtab;
+    a.dinv = dinv; a.scale = CHEB ? cheb[0] : scale; a.ctab = ctab; a.dtab = dtab;
+    if (CHEB) for (int q = 0; q < 6; q++) a.ch[q] = cheb[1 + q];
     if (rout) { if (!NORM || rout == unew || rout == u || rout == b) return fail(MGK_EINVAL, "mgk_jacobi3_2d_sumsq_store_f64: bad arguments"); a.rout = rout + g->org; }
     a.ntx = ((g->nx + 1) / 2 + 59) / 60;                      // pairs 0 .. (nx-1)/2
     // levels that fit the caches (rows of <= 1024): short chunks with every load up front (they lack waves, not bandwidth); the big
@@ -299,7 +314,7 @@ static int jacobi3_2d(mgk_ctx *c, const mgk_geom *g, const mgk_geom *gc, const d
         *norm_parts = (int)(4 * nblk);
     }
     hipStream_t st = S(c, stream);
-#define J3_LAUNCH(TABV, YCV) hipLaunchKernelGGL((k_jacobi3_2d<PRO, ZG, NORM, TABV, YCV>), dim3(nblk), dim3(256), 0, st, a)
+#define J3_LAUNCH(TABV, YCV) hipLaunchKernelGGL((k_jacobi3_2d<PRO, ZG, NORM, TABV, YCV, CHEB>), dim3(nblk), dim3(256), 0, st, a)
     if (ctab) { if (ycs == 4) J3_LAUNCH(true, 4); else if (ycs == 8) J3_LAUNCH(true, 8); else J3_LAUNCH(true, 0); }
     else { if (ycs == 4) J3_LAUNCH(false, 4); else if (ycs == 8) J3_LAUNCH(false, 8); else J3_LAUNCH(false, 0); }
 #undef J3_LAUNCH
@@ -333,6 +348,28 @@ extern "C" int mgk_jacobi3_2d_zero_f64(mgk_ctx *c, const mgk_geom *g, const doub
 extern "C" int mgk_prolong_jacobi3_2d_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
                                           const double *ctab, const double *dtab, const double *b, const double *uc, const double *u, double *unew, void *stream) {
     return jacobi3_2d<true, false, false>(c, gf, gc, coef, dinv, scale, ctab, dtab, b, uc, u, unew, stream, nullptr);
+}
+// The same passes with the three steps of a restarted Chebyshev recurrence as their stages (k_jacobi3_2d<..., CHEB>): a whole
+// KSPSolve(KSPCHEBYSHEV, max_it = 3) in one pass.  cheb = {s, c_km1, c_k, c_z of step 2, c_km1, c_k, c_z of step 3}
+extern "C" int mgk_cheby3_2d_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, const double *cheb, const double *ctab, const double *dtab,
+                                 const double *b, const double *u, double *unew, void *stream) {
+    return jacobi3_2d<false, false, false, true>(c, g, nullptr, coef, dinv, 0.0, ctab, dtab, b, nullptr, u, unew, stream, nullptr, nullptr, cheb);
+}
+extern "C" int mgk_cheby3_2d_sumsq_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, const double *cheb, const double *ctab, const double *dtab,
+                                       const double *b, const double *u, double *unew, double *sumsq_host, void *stream) {
+    if (!sumsq_host) return fail(MGK_EINVAL, "mgk_cheby3_2d_sumsq_f64: bad arguments");
+    int nparts = 0;
+    int rc = jacobi3_2d<false, false, true, true>(c, g, nullptr, coef, dinv, 0.0, ctab, dtab, b, nullptr, u, unew, stream, &nparts, nullptr, cheb);
+    if (rc) return rc;
+    return finish_to_host(c, nparts, 1, S(c, stream), sumsq_host);
+}
+extern "C" int mgk_cheby3_2d_zero_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, const double *cheb, const double *ctab, const double *dtab,
+                                      const double *b, double *unew, void *stream) {
+    return jacobi3_2d<false, true, false, true>(c, g, nullptr, coef, dinv, 0.0, ctab, dtab, b, nullptr, nullptr, unew, stream, nullptr, nullptr, cheb);
+}
+extern "C" int mgk_prolong_cheby3_2d_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, const double *cheb,
+                                         const double *ctab, const double *dtab, const double *b, const double *uc, const double *u, double *unew, void *stream) {
+    return jacobi3_2d<true, false, false, true>(c, gf, gc, coef, dinv, 0.0, ctab, dtab, b, uc, u, unew, stream, nullptr, nullptr, cheb);
 }
 // FMG interpolation (full multigrid), uniform mesh: unew = J(J(J(0 + P uc))) -- the interpolated coarse solution as the new iterate and the
 // three pre-smoothing sweeps of the V-cycle that starts from it, in one pass over b and uc (the old unew is never read).  Any 2-D grid

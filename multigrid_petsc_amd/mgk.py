@@ -133,6 +133,12 @@ def _sigs(L):
         "mgk_jacobi3_2d_zero_f64": (i, [vp, G, c_dp, d, d, vp, vp, vp, vp, vp]),
         "mgk_jacobi3_2d_sumsq_store_f64": (i, [vp, G, c_dp, d, d, vp, vp, vp, vp, vp, vp, C.POINTER(d), vp]),
         "mgk_prolong_jacobi3_2d_f64": (i, [vp, G, G, c_dp, d, d, vp, vp, vp, vp, vp, vp, vp]),
+        # KSPCHEBYSHEV with max_it = 3 in one pass: cheb = 7 doubles {s, (c_km1, c_k, c_z) of step 2, of step 3} in place of scale
+        "mgk_cheby3_2d_f64": (i, [vp, G, c_dp, d, c_dp, vp, vp, vp, vp, vp, vp]),
+        "mgk_cheby3_2d_sumsq_f64": (i, [vp, G, c_dp, d, c_dp, vp, vp, vp, vp, vp, C.POINTER(d), vp]),
+        "mgk_cheby3_2d_zero_f64": (i, [vp, G, c_dp, d, c_dp, vp, vp, vp, vp, vp]),
+        "mgk_prolong_cheby3_2d_f64": (i, [vp, G, G, c_dp, d, c_dp, vp, vp, vp, vp, vp, vp, vp]),
+        "mgk_tail_cycle_cheby_f64": (i, [vp, G, i, C.POINTER(i), c_dp, c_dp, C.POINTER(vp), C.POINTER(vp), d, d, i, i, vp, vp, vp]),
         "mgk_sweep_residual_restrict_2d_f64": (i, [vp, G, G, c_dp, d, d, vp, vp, vp, vp, vp, d, d, vp]),
         "mgk_jacobi2_sumsq_slab_f64": (i, [vp, G, G, c_dp, d, d, vp, vp, vp, vp, i, i, i, i, i, C.POINTER(i), vp]),
         "mgk_jacobi2_sumsq_mid_slab_f64": (i, [vp, G, G, c_dp, d, d, vp, vp, vp, vp, i, i, i, i, i, C.POINTER(i), vp]),
