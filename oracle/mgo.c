@@ -857,7 +857,10 @@ static void residual(const mgo_vcycle_cfg *c, olevel *L) {     /* KSPBuildResidu
     else mgo_st_residual(c->dim, L->n, L->n, L->As, L->b, L->u, NULL, NULL, L->rv);
 }
 
-int mgo_vcycle(const mgo_vcycle_cfg *c, double *rnorm, double *u_out, double *bnorm_out, double *solve_seconds) {
+/* b_in: the right-hand side on the fine grid (N0 doubles, used as it is on either leg and any mesh), or NULL for the
+ * manufactured one of solver.c:558-620 */
+int mgo_vcycle_b(const mgo_vcycle_cfg *c, const double *b_in, double *rnorm, double *u_out, double *bnorm_out,
+                 double *solve_seconds) {
     int levels = c->levels, dim = c->dim;
     olevel *L = (olevel *)calloc(levels, sizeof(olevel));
     for (int l = 0; l < levels; l++) {
@@ -875,7 +878,8 @@ int mgo_vcycle(const mgo_vcycle_cfg *c, double *rnorm, double *u_out, double *bn
             if (l < levels - 1) { L[l].R = mgo_build_R(dim, c->npts, l); L[l].P = mgo_build_P(dim, c->npts, l); }
         }
     }
-    if (c->mesh != 0 && dim == 2 && c->use_csr) mgo_rhs_mesh(c->npts, c->mesh, L[0].b);
+    if (b_in) memcpy(L[0].b, b_in, sizeof(double) * L[0].N);
+    else if (c->mesh != 0 && dim == 2 && c->use_csr) mgo_rhs_mesh(c->npts, c->mesh, L[0].b);
     else mgo_rhs(dim, c->npts, L[0].b);                             /* levelvecb */
     double bnorm = mgo_norm2(L[0].b, L[0].N);                       /* solver.c:1512 */
     memset(L[0].u, 0, sizeof(double) * L[0].N);                     /* :1514 */
@@ -924,6 +928,10 @@ int mgo_vcycle(const mgo_vcycle_cfg *c, double *rnorm, double *u_out, double *bn
     }
     free(L);
     return iter;
+}
+
+int mgo_vcycle(const mgo_vcycle_cfg *c, double *rnorm, double *u_out, double *bnorm_out, double *solve_seconds) {
+    return mgo_vcycle_b(c, NULL, rnorm, u_out, bnorm_out, solve_seconds);
 }
 
 

@@ -145,6 +145,10 @@ typedef struct mgo_vcycle_cfg {
  * returns number of cycles done (solver->numIter, solver.c:1558); bnorm_out = ||b0||. */
 int mgo_vcycle(const mgo_vcycle_cfg *cfg, double *rnorm_raw, double *u_out, double *bnorm_out,
                double *solve_seconds);
+/* the same with the fine-grid right-hand side from the caller: b_in = N0 doubles, used as it is (on the assembled leg and a
+ * stretched mesh too); b_in == NULL is the manufactured right-hand side, i.e. mgo_vcycle */
+int mgo_vcycle_b(const mgo_vcycle_cfg *cfg, const double *b_in, double *rnorm_raw, double *u_out, double *bnorm_out,
+                 double *solve_seconds);
 /* -cycle 8 (src/solver.c:1884-1989): outer Richardson + textbook PCMG V-cycle with cfg's smoother on every level
  * (v0 sweeps, v1 on the coarsest grid).  PETSc-internal semantics, version unpinned: PARITY UNPINNED. */
 int mgo_pcmg(const mgo_vcycle_cfg *cfg, double *rnorm_raw, double *u_out, double *bnorm_out,
@@ -166,6 +170,8 @@ void mgo_st_residual_f32_thin(int nx, int ny, int nz, const float *As, const flo
 void mgo_st_restrict_f32_thin(int nxf, int nyf, int nzf, int nzc, const float *rf, float *bc);
 void mgo_st_prolong_add_f32_thin(int nxf, int nyf, int nzf, int nzc, const float *uc, float *uf);
 int  mgo_vcycle_mixed(const mgo_vcycle_cfg *cfg, double *rnorm_raw, double *u_out, double *bnorm_out, double *solve_seconds);
+int  mgo_vcycle_mixed_b(const mgo_vcycle_cfg *cfg, const double *b_in, double *rnorm_raw, double *u_out, double *bnorm_out,
+                        double *solve_seconds);   /* b_in == NULL: the manufactured right-hand side */
 
 #ifdef __cplusplus
 }

@@ -139,7 +139,8 @@ static void smooth32(l32 *L, int its, float scale, int guess_nonzero) {
 }
 
 /* returns outer iterations; rnorm: fp64 ||b - A u|| per outer iteration */
-int mgo_vcycle_mixed(const mgo_vcycle_cfg *c, double *rnorm, double *u_out, double *bnorm_out, double *solve_seconds) {
+int mgo_vcycle_mixed_b(const mgo_vcycle_cfg *c, const double *b_in, double *rnorm, double *u_out, double *bnorm_out,
+                       double *solve_seconds) {
     const int levels = c->levels, dim = 3;
     if (c->dim != 3 || c->ksp_type != 0) return -1;
     int n0 = mgo_grid_n(c->npts, 0);
@@ -159,7 +160,8 @@ int mgo_vcycle_mixed(const mgo_vcycle_cfg *c, double *rnorm, double *u_out, doub
         L[l].rv = (float *)calloc(L[l].N, sizeof(float)); L[l].tmp = (float *)calloc(L[l].N, sizeof(float));
     }
     const float scale = (float)c->scale;
-    mgo_rhs(dim, c->npts, b);
+    if (b_in) memcpy(b, b_in, sizeof(double) * N0);
+    else mgo_rhs(dim, c->npts, b);
     double bnorm = mgo_norm2(b, N0);
     mgo_st_residual(dim, n0, n0, As0, b, u, NULL, NULL, r);
     double rchk = mgo_norm2(r, N0);
@@ -195,4 +197,8 @@ int mgo_vcycle_mixed(const mgo_vcycle_cfg *c, double *rnorm, double *u_out, doub
     for (int l = 0; l < levels; l++) { free(L[l].u); free(L[l].b); free(L[l].rv); free(L[l].tmp); }
     free(L); free(u); free(b); free(r);
     return iter;
+}
+
+int mgo_vcycle_mixed(const mgo_vcycle_cfg *c, double *rnorm, double *u_out, double *bnorm_out, double *solve_seconds) {
+    return mgo_vcycle_mixed_b(c, NULL, rnorm, u_out, bnorm_out, solve_seconds);
 }

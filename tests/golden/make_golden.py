@@ -7,6 +7,7 @@ loops.  It shares no code with oracle/ or with the product; it runs only in the 
 (scipy is not needed on the GPU box) and its outputs are committed as data.
 
     python tests/golden/make_golden.py          # rewrites tests/golden/vcycle_golden.npz
+    python tests/golden/make_golden.py --rhs    # rewrites tests/golden/vcycle_rhs_golden.npz (stored right-hand sides, main_rhs)
 
 What is restated (reference file:line):
   operator rows      src/solver.c:185-253 + src/problem.c:3-22 (uniform mesh: 1/h^2 second differences)
@@ -181,7 +182,8 @@ def richardson(A, dinv, b, x, maxit, scale, guess_nonzero):
     return x
 
 
-def vcycle(dim, npts, levels, v0, v1, scale, maxiter=400, rtol=1e-7, mesh=0):
+def vcycle(dim, npts, levels, v0, v1, scale, maxiter=400, rtol=1e-7, mesh=0, b=None):
+    """b: the fine-grid right-hand side, taken as it is (on the stretched meshes too); None: the manufactured one"""
     ns = [(npts - 1) // 2 ** l - 1 for l in range(levels)]
     A = [level_operator(dim, n) for n in ns] if mesh == 0 else [level_operator_mesh(npts, l, mesh) for l in range(levels)]
     dinv = [1.0 / a.diagonal() for a in A]
@@ -189,7 +191,9 @@ def vcycle(dim, npts, levels, v0, v1, scale, maxiter=400, rtol=1e-7, mesh=0):
     P = [sp.csr_matrix((2.0 ** dim) * r.T) for r in R]
     for p in P:
         p.sort_indices()
-    b = [rhs(dim, npts) if mesh == 0 else rhs_mesh(npts, mesh)] + [None] * (levels - 1)
+    if b is None:
+        b = rhs(dim, npts) if mesh == 0 else rhs_mesh(npts, mesh)
+    b = [np.array(b, dtype=np.float64)] + [None] * (levels - 1)
     u = [np.zeros(n ** dim) for n in ns]
     bnorm = math.sqrt(float(np.dot(b[0], b[0])))
     r0 = b[0] - A[0] @ u[0]
@@ -288,5 +292,38 @@ def main():
     print("wrote", os.path.join(HERE, "vcycle_golden.npz"), len(out), "arrays")
 
 
+RHS_CASES = [  # dim, npts, levels, scale, mesh
+    (2, 33, 5, 0.8, 0), (3, 17, 4, 6.0 / 7.0, 0), (2, 33, 4, 0.8, 1), (2, 33, 4, 0.8, 2),
+]
+
+
+def main_rhs():
+    """tests/golden/vcycle_rhs_golden.npz: the same restatement on right-hand sides that are NOT the manufactured mode (tests/rhs_cases.py:
+    rough uniform data, a handful of +-1 spikes).  b itself is stored: the test that reads the file does not depend on a generator's stream."""
+    import sys
+    sys.path.insert(0, os.path.dirname(HERE))
+    import rhs_cases
+    out = {}
+    for dim, npts, levels, scale, mesh in RHS_CASES:
+        for family in rhs_cases.FAMILIES:
+            b = rhs_cases.make(family, dim, npts, seed=0x5EED0002 + 16 * npts + mesh)
+            r = vcycle(dim, npts, levels, 3, 3, scale, maxiter=1000, mesh=mesh, b=b)
+            key = ("mesh%d_n%d_l%d" % (mesh, npts, levels) if mesh else "d%d_n%d_l%d" % (dim, npts, levels)) + "_" + family
+            thr = 1e-7 * r["bnorm"]
+            assert r["iters"] < 1000 and not (1 - 1e-6 < r["rnorm"][-1] / thr < 1 + 1e-6) and not (1 - 1e-6 < r["rnorm"][-2] / thr < 1 + 1e-6)
+            out[key + "_meta"] = np.array([dim, npts, levels, 3, 3, 1000, r["iters"], mesh], dtype=np.int64)
+            out[key + "_scale"] = np.array([scale, r["bnorm"]])
+            out[key + "_rnorm"] = r["rnorm"]
+            out[key + "_b"] = b
+            out[key + "_u"] = r["u"]
+            print(key, "cycles", r["iters"], "last / threshold", r["rnorm"][-1] / thr, "before it", r["rnorm"][-2] / thr)
+    np.savez_compressed(os.path.join(HERE, "vcycle_rhs_golden.npz"), **out)
+    print("wrote", os.path.join(HERE, "vcycle_rhs_golden.npz"), len(out), "arrays")
+
+
 if __name__ == "__main__":
-    main()
+    import sys
+    if "--rhs" in sys.argv[1:]:                   # python tests/golden/make_golden.py --rhs    rewrites vcycle_rhs_golden.npz only
+        main_rhs()
+    else:
+        main()

@@ -39,6 +39,8 @@ class Oracle:
         for f in ("mgo_build_A", "mgo_build_R", "mgo_build_P"):
             getattr(L, f).restype = C.c_void_p
             getattr(L, f).argtypes = [C.c_int, C.c_int, C.c_int]
+        L.mgo_build_A_mesh.restype = C.c_void_p
+        L.mgo_build_A_mesh.argtypes = [C.c_int, C.c_int, C.c_int]
         L.mgo_csr_free.argtypes = [C.c_void_p]
         for f in ("mgo_csr_nrows", "mgo_csr_ncols", "mgo_csr_nnz"):
             getattr(L, f).restype = C.c_long
@@ -57,8 +59,11 @@ class Oracle:
         L.mgo_st_prolong_add.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
         L.mgo_vcycle.restype = C.c_int
         L.mgo_vcycle.argtypes = [C.POINTER(VcycleCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.mgo_vcycle_b.restype = C.c_int
+        L.mgo_vcycle_b.argtypes = [C.POINTER(VcycleCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.mgo_level_stencil.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         L.mgo_rhs.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.mgo_rhs_mesh.argtypes = [C.c_int, C.c_int, C.c_void_p]
         L.mgo_error_norms.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.mgo_coords_uniform.argtypes = [C.c_int, C.c_int, C.c_void_p]
         L.mgo_get_ranges.argtypes = [C.c_int, C.c_int, C.c_void_p]
@@ -88,6 +93,8 @@ class Oracle:
         L.mgo_icycle.argtypes = [C.POINTER(VcycleCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.mgo_vcycle_mixed.restype = C.c_int
         L.mgo_vcycle_mixed.argtypes = [C.POINTER(VcycleCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.mgo_vcycle_mixed_b.restype = C.c_int
+        L.mgo_vcycle_mixed_b.argtypes = [C.POINTER(VcycleCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
 
     # ---- conveniences ----
     def level_stencil(self, dim, npts, l):
@@ -99,6 +106,11 @@ class Oracle:
     def rhs(self, dim, npts):
         b = np.zeros((npts - 2) ** dim)
         self.L.mgo_rhs(dim, npts, _p(b))
+        return b
+
+    def rhs_mesh(self, npts, mesh):
+        b = np.zeros((npts - 2) ** 2)
+        self.L.mgo_rhs_mesh(npts, mesh, _p(b))
         return b
 
     def coords(self, npts):
@@ -166,13 +178,25 @@ class Oracle:
         x = np.ascontiguousarray(x)
         return self.L.mgo_sumsq(_p(x), x.size)
 
+    @staticmethod
+    def _rhs_arg(b, size):
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+        if b.size != size:
+            raise ValueError(f"oracle: right-hand side needs {size} values, got {b.size}")
+        return b
+
     def vcycle(self, dim, npts, levels, v0=3, v1=3, maxiter=1000, ksp_type=0, scale=1.0, emin=0.0, emax=0.0,
-               use_csr=0, fixed_cycles=0, rtol=0.0, want_u=True, mesh=0):
+               use_csr=0, fixed_cycles=0, rtol=0.0, want_u=True, mesh=0, b=None):
+        """b: the fine-grid right-hand side ((npts-2)**dim doubles, used as it is); None = the manufactured one"""
         cfg = VcycleCfg(dim, npts, levels, v0, v1, maxiter, ksp_type, scale, emin, emax, use_csr, fixed_cycles, rtol, mesh)
         rn = np.zeros(max(maxiter, fixed_cycles) + 1)
         u = np.zeros((npts - 2) ** dim) if want_u else None
         bn, sec = C.c_double(), C.c_double()
-        it = self.L.mgo_vcycle(C.byref(cfg), _p(rn), _p(u), C.byref(bn), C.byref(sec))
+        if b is None:
+            it = self.L.mgo_vcycle(C.byref(cfg), _p(rn), _p(u), C.byref(bn), C.byref(sec))
+        else:
+            b = self._rhs_arg(b, (npts - 2) ** dim)
+            it = self.L.mgo_vcycle_b(C.byref(cfg), _p(b), _p(rn), _p(u), C.byref(bn), C.byref(sec))
         return {"iters": it, "rnorm": rn[:it + 1].copy(), "u": u, "bnorm": bn.value, "seconds": sec.value}
 
     def pcmg(self, dim, npts, levels, v0=3, v1=3, maxiter=1000, ksp_type=0, scale=1.0, emin=0.0, emax=0.0, use_csr=0):
@@ -254,12 +278,16 @@ class Oracle:
             self.L.mgo_st_prolong_add_f32_thin(nf, nyfv, nzfv, nzcv, _p(uc), _p(out))
         return out
 
-    def vcycle_mixed(self, npts, levels, v0=3, v1=3, maxiter=100, scale=1.0, fixed_cycles=0):
+    def vcycle_mixed(self, npts, levels, v0=3, v1=3, maxiter=100, scale=1.0, fixed_cycles=0, b=None):
         cfg = VcycleCfg(3, npts, levels, v0, v1, maxiter, 0, scale, 0.0, 0.0, 0, fixed_cycles, 0.0, 0)
         rn = np.zeros(max(maxiter, fixed_cycles) + 1)
         u = np.zeros((npts - 2) ** 3)
         bn, sec = C.c_double(), C.c_double()
-        it = self.L.mgo_vcycle_mixed(C.byref(cfg), _p(rn), _p(u), C.byref(bn), C.byref(sec))
+        if b is None:
+            it = self.L.mgo_vcycle_mixed(C.byref(cfg), _p(rn), _p(u), C.byref(bn), C.byref(sec))
+        else:
+            b = self._rhs_arg(b, (npts - 2) ** 3)
+            it = self.L.mgo_vcycle_mixed_b(C.byref(cfg), _p(b), _p(rn), _p(u), C.byref(bn), C.byref(sec))
         return {"iters": it, "rnorm": rn[:it + 1].copy(), "u": u, "bnorm": bn.value, "seconds": sec.value}
 
     # CSR handles

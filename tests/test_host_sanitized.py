@@ -167,6 +167,40 @@ def test_slab_ranks_under_sanitizers(san, tmp_path, P, npts, levels, dmin, extra
             assert int(m.group(7)) > 0 and int(m.group(8)) > 0, out[-400:]
 
 
+@pytest.mark.parametrize("P,npts,levels,dmin,mode,families", [
+    (2, 33, 4, 15, "rhs", ("uniform", "spikes")), (3, 33, 4, 15, "rhs", ("spikes", "uniform")), (3, 33, 5, 7, "rhs", ("spikes", "spikes")),
+    (4, 65, 5, 15, "rhs", ("uniform", "uniform")), (8, 65, 4, 31, "rhs", ("spikes", "uniform")), (2, 33, 4, 15, "rhs_mixed", ("uniform", "spikes")),
+])
+def test_slab_ranks_replace_the_right_hand_side_under_sanitizers(san, tmp_path, P, npts, levels, dmin, mode, families):
+    """mg_solver_set_rhs_host on slab ranks under ASan / UBSan: each rank uploads its own planes [z0, z0 + nz) of a global b (tests/rhs_cases.py; the
+    spikes sit on both planes next to every even plane index, where the cuts fall), solves, loads a SECOND right-hand side into the live solver -- the
+    neighbours' b ghost planes and far planes are caches of the first -- and solves again.  tests/san_slab.c: ranks equal the single rank, the live
+    solver equals a fresh one bit for bit; here: the single rank's two results equal the oracle's on those right-hand sides."""
+    import rhs_cases
+    orc = Oracle()
+    n = npts - 2
+    cuts = list(range(2, n - 1, 2))               # slab starts are even (DESIGN.md "decomposition"): whichever of them the ranks are cut at
+    refs = []
+    for q, fam in enumerate(families):
+        seed = 3000 + 10 * npts + q
+        while True:
+            b = rhs_cases.make(fam, 3, npts, seed, cuts if fam == "spikes" else ())
+            ref = (orc.vcycle_mixed(npts, levels, 3, 3, maxiter=60, scale=6.0 / 7.0, b=b) if mode == "rhs_mixed"
+                   else orc.vcycle(3, npts, levels, 3, 3, maxiter=60, scale=6.0 / 7.0, b=b))
+            if rhs_cases.stop_rule_clear(ref):
+                break
+            seed += 1000                                                       # (never skipped: another seed)
+        rhs_cases.assert_stop_rule_clear(ref, maxiter=60)
+        b.tofile(tmp_path / f"b{q + 1}.bin")
+        refs.append(ref)
+    out = _run(san["slab"], [str(P), str(npts), str(levels), str(dmin), mode, str(tmp_path / "b1.bin"), str(tmp_path / "b2.bin"), str(tmp_path / "out")], tmp_path)
+    assert f"SAN_SLAB_RHS_OK P={P} cycles={refs[0]['iters']},{refs[1]['iters']}" in out, out[-2000:]
+    for q, ref in enumerate(refs):
+        u, rn = np.fromfile(tmp_path / f"out{q + 1}.u"), np.fromfile(tmp_path / f"out{q + 1}.rn")
+        assert np.array_equal(u, ref["u"])
+        assert rn.shape == ref["rnorm"].shape and np.abs(rn / ref["rnorm"] - 1).max() <= 1e-12
+
+
 @pytest.mark.parametrize("P,npts,levels,dmin", [(2, 33, 4, 15), (3, 33, 4, 15), (8, 65, 4, 31)])
 def test_slab_ranks_over_the_peer_transport_under_sanitizers(san, tmp_path, P, npts, levels, dmin):
     """the peer transport's host logic (csrc/mg_comm.c: mailbox slots, flag words and their sequence numbers, gather box, all-reduce slots)

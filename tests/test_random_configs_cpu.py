@@ -19,6 +19,17 @@ def test_random_solver_configurations_on_the_host_mock_equal_the_oracle():
     assert "REFUSED" not in p.stdout, p.stdout[-3000:]
 
 
+@pytest.mark.timeout(600)
+def test_random_solver_configurations_on_arbitrary_right_hand_sides_on_the_host_mock_equal_the_oracle():
+    """the same draws in the tool's rhs mode: a right-hand side of tests/rhs_cases.py through mg_solver_set_rhs_host (rough uniform data, spikes, or the
+    manufactured one), and in half the draws a second one loaded into the live solver object -- equal to the oracle on that right-hand side, and the
+    second result equal to a fresh solver's bit for bit, norms included"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "stress_solver_mock.py"), "150", "101", "rhs"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, timeout=500, cwd=ROOT)
+    assert p.returncode == 0 and "150 configurations, 0 mismatches" in p.stdout, p.stdout[-3000:]
+    assert "REFUSED" not in p.stdout, p.stdout[-3000:]
+
+
 @pytest.mark.timeout(900)
 def test_random_reference_driver_options_on_the_host_mock_equal_the_oracle(tmp_path):
     exe = os.path.join(ROOT, "tests", "_san", "san_refdriver")
@@ -43,3 +54,16 @@ def test_ninety_one_byte_fine_level_on_slab_ranks_over_the_host_mock():
     assert p.returncode == 0 and "bad 0" in p.stdout, p.stdout[-3000:]
     m = __import__("re").search(r"pj2_slab=(\d+) mid_slab=(\d+)", p.stdout)
     assert m and int(m.group(1)) > 0 and int(m.group(2)) > 0, p.stdout[-500:]          # the new passes did run
+
+
+@pytest.mark.timeout(900)
+def test_slab_ranks_on_arbitrary_right_hand_sides_over_the_host_mock():
+    """tools/stress_slab91.py in its rhs mode: every rank passes mg_solver_set_rhs_host its own planes [z0, z0 + nz) of a global right-hand side (uniform, or
+    spikes on both planes next to every rank cut); half the runs replace it on the live solvers.  Iteration counts, histories and the concatenated slabs
+    equal the oracle's on that right-hand side; the second result equals fresh solvers' bit for bit."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "stress_slab91.py"), "", "rhs"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=800,
+                       cwd=ROOT, env=dict(os.environ, MOCK="1", MOCK_MGK_STATS="1"))
+    assert p.returncode == 0 and "bad 0" in p.stdout, p.stdout[-3000:]
+    assert p.stdout.count("OK ") == 28 and p.stdout.count("on the live solvers") >= 7, p.stdout[-3000:]
+    m = __import__("re").search(r"pj2_slab=(\d+) mid_slab=(\d+)", p.stdout)
+    assert m and int(m.group(1)) > 0 and int(m.group(2)) > 0, p.stdout[-500:]          # the 91-byte passes did run on these right-hand sides

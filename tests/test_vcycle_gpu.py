@@ -120,6 +120,9 @@ def test_fixed_cycles_and_random_rhs(orc):
     assert s.iterations == 4
     r = s.rnorm
     assert np.all(np.diff(r) < 0)          # contracts every cycle
+    ref = orc.vcycle(3, 17, 3, 3, 3, scale=0.8, fixed_cycles=4, b=b)       # (larger sizes, every path: tests/test_rhs_cycle_gpu.py)
+    assert abs(s.bnorm - ref["bnorm"]) <= RTOL * ref["bnorm"] and np.abs(r / ref["rnorm"] - 1).max() <= RTOL
+    assert np.array_equal(s.solution(), ref["u"])
     s.close()
 
 
