@@ -103,6 +103,7 @@ def _sigs(L):
         "mgk_csr_mult_f64": (i, [vp, C.c_long, vp, vp, vp, vp, vp, d, vp, i, C.c_long, C.c_long, vp]),
         "mgk_jacobi_zero_rowcoef_f64": (i, [vp, G, vp, d, vp, vp, vp]),
         "mgk_rowcoef_f64": (i, [vp, G, i, vp, vp, d, vp, vp, vp, vp]),
+        "mgk_cheby_rowcoef_f64": (i, [vp, G, vp, vp, d, d, d, vp, vp, vp, vp, vp]),
         "mgk_jacobi_range_f64": (i, [vp, G, c_dp, d, d, vp, vp, vp, i, i, vp]),
         "mgk_jacobi2_slab_f64": (i, [vp, G, G, c_dp, d, d, vp, vp, vp, vp, i, i, i, i, vp]),
         "mgk_prolong_jacobi_f64": (i, [vp, G, G, c_dp, d, d, vp, vp, vp, vp, vp]),

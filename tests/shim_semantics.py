@@ -781,6 +781,187 @@ def random_programs_keep_petsc_semantics(L, orc, seed=1, nprog=40, nops=60):
         L.PetscFinalize()
 
 
+def _five_point(n, row_coef):
+    """dense n^2 x n^2 five-point operator in lexicographic numbering, row_coef(i) = {(i-1), W, C, E, (i+1)} of grid row i; neighbours
+    outside the grid are absent (src/solver.c:239-251)"""
+    M = np.zeros((n * n, n * n))
+    for i in range(n):
+        c = row_coef(i)
+        for j in range(n):
+            r = i * n + j
+            if i > 0:
+                M[r, r - n] = c[0]
+            if j > 0:
+                M[r, r - 1] = c[1]
+            M[r, r] = c[2]
+            if j < n - 1:
+                M[r, r + 1] = c[3]
+            if i < n - 1:
+                M[r, r + n] = c[4]
+    return M
+
+
+def _transfer_pair(nf):
+    """dense full weighting ([1 2 1; 2 4 2; 1 2 1] / 16) and bilinear prolongation between nf^2 and ((nf - 1) / 2)^2 unknowns"""
+    nc = (nf - 1) // 2
+    r1 = np.zeros((nc, nf))
+    for i in range(nc):
+        r1[i, 2 * i:2 * i + 3] = (0.25, 0.5, 0.25)
+    return np.kron(r1, r1), np.kron(2.0 * r1.T, 2.0 * r1.T)
+
+
+def _device_operator(L, m):
+    """what MatView prints for the matrix: the line that names the device operator the drop-in chose"""
+    import os
+    import sys
+    import tempfile
+    L.MatView.argtypes = [C.c_void_p, C.c_void_p]
+    sys.stdout.flush()
+    with tempfile.TemporaryFile() as t:
+        saved = os.dup(1)
+        os.dup2(t.fileno(), 1)
+        try:
+            L.MatView(m, None)
+        finally:
+            os.dup2(saved, 1)
+            os.close(saved)
+        t.seek(0)
+        return t.read().decode()
+
+
+def nonsymmetric_operators_keep_petsc_semantics(L, orc):
+    """Operators the Poisson problem never assembles: a constant five-point matrix with five DISTINCT values and a row-dependent one with
+    W != E (tests/coef_cases.py), through MatSetValue.  recognise_stencil / recognise_stencil_rowvar take them (MatView names the device
+    operator: no AIJ kernel) and hand the five values to the fused kernels; with the Poisson operators' equal off-diagonals a transposed
+    pair on that way would not show.  MatMult, MatResidual / KSPBuildResidual + VecNorm, KSPSolve (Richardson + Jacobi, max_it 1 .. 4 --
+    3 takes the three-sweep passes --, zero and nonzero guess), the norm pass followed by an adopting solve, and a two-level step in the
+    reference's order (src/solver.c:1531-1546) with a distinct-coefficient coarse operator, against dense numpy.  Tolerance: 1e-11 of the
+    vector's magnitude, as random_programs_keep_petsc_semantics; a swapped coefficient moves the result by O(1).
+    Sizes: 17^2 and 65^2 unknowns (coarse grids 8^2 / 32^2: even, so the coarse operator and the transfers to it run on the AIJ kernel), and
+    15^2 / 63^2 (coarse 7^2 / 31^2: all four recognised, so the fused residual + restriction starts the coarse level with ITS constants and
+    the prolongation is fused into the post-smoothing pass)."""
+    from coef_cases import distinct_coef, distinct_row_tables
+    L.PetscInitialize(None, None, None, None)
+    L.PetscOptionsSetValue(None, b"-pc_type", b"jacobi")
+    rng = np.random.default_rng(29)
+    STENCIL, ROWVAR, AIJ = "matrix-free 5-point stencil\n", "matrix-free 5-point stencil with row-dependent coefficients\n", "assembled AIJ"
+
+    def operator(n, form):
+        if form == "constant":
+            c = distinct_coef(rng, 2)
+            return _five_point(n, lambda i: c)
+        ct, _ = distinct_row_tables(rng, n)
+        return _five_point(n, lambda i: ct[i])
+
+    def close(got, want, what):
+        err = float(np.max(np.abs(got - want)))
+        assert err <= 1e-11 * max(1.0, float(np.abs(want).max())), (what, err)
+
+    def norm_close(val, want, what):
+        assert abs(val - np.linalg.norm(want)) <= 1e-11 * np.sqrt(want.size) * max(1.0, float(np.abs(want).max())), (what, val, np.linalg.norm(want))
+
+    for n in (17, 65, 15, 63):
+        nc = (n - 1) // 2
+        Rm, Pm = _transfer_pair(n)
+        mR, mP = _assemble(L, Rm), _assemble(L, Pm)
+        if nc % 2:
+            assert "full weighting" in _device_operator(L, mR) and "bilinear prolongation" in _device_operator(L, mP)
+        else:               # (no padded layout for an even grid: the transfers to it are AIJ matrices as well)
+            assert AIJ in _device_operator(L, mR) and AIJ in _device_operator(L, mP)
+        for form in ("constant", "rowvar"):
+            tag = f"n={n} {form}"
+            A, Ac = operator(n, form), operator(nc, form)
+            assert not np.allclose(A, A.T)
+            mA, mAc = _assemble(L, A), _assemble(L, Ac)
+            kind = _device_operator(L, mA)
+            assert kind.endswith(STENCIL if form == "constant" else ROWVAR) and AIJ not in kind, (tag, kind)
+            kind_c = _device_operator(L, mAc)
+            if nc % 2:
+                assert kind_c.endswith(STENCIL if form == "constant" else ROWVAR) and AIJ not in kind_c, (tag, kind_c)
+            else:
+                assert AIJ in kind_c, (tag, kind_c)
+            nf, ncc = n * n, nc * nc
+            d, dc = 1.0 / np.diag(A), 1.0 / np.diag(Ac)
+            xv, bv, uv = rng.uniform(-1, 1, nf), rng.uniform(-1, 1, nf), rng.uniform(-1, 1, nf)
+            x, b, u, r, rv, y = (C.c_void_p() for _ in range(6))
+            uc, bc = C.c_void_p(), C.c_void_p()
+            L.MatCreateVecs(mA, C.byref(x), C.byref(b))
+            for v in (u, r, rv, y):
+                L.VecDuplicate(x, C.byref(v))
+            L.MatCreateVecs(mAc, C.byref(uc), C.byref(bc))
+            val, V = C.c_double(), C.c_void_p()
+
+            def sweeps(M, dinv, x0, rhs, m, s):
+                for _ in range(m):
+                    x0 = x0 + s * (dinv * (rhs - M @ x0))
+                return x0
+
+            def solver(mat, maxit, scale, guess):
+                k = C.c_void_p()
+                L.KSPCreate(1, C.byref(k))
+                L.KSPSetType(k, b"richardson"); L.KSPSetOperators(k, mat, mat); L.KSPSetNormType(k, 0)
+                L.KSPSetTolerances(k, 1e-7, -2.0, -2.0, maxit)
+                L.KSPSetFromOptions(k)
+                L.KSPRichardsonSetScale(k, scale)
+                L.KSPSetInitialGuessNonzero(k, guess)
+                return k
+
+            # MatMult, MatResidual + VecNorm
+            _set(L, x, xv); _set(L, b, bv)
+            L.MatMult(mA, x, y)
+            close(_get(L, y, nf), A @ xv, f"{tag}: MatMult")
+            L.MatResidual(mA, b, x, r)
+            L.VecNorm(r, NORM_2, C.byref(val))
+            norm_close(val.value, bv - A @ xv, f"{tag}: MatResidual + VecNorm")
+            close(_get(L, r, nf), bv - A @ xv, f"{tag}: MatResidual")
+            # KSPSolve: sweeps from the zero guess and from a nonzero one; KSPBuildResidual + VecNorm; the norm pass and the adopting solve
+            for maxit in (1, 2, 3, 4):
+                for guess in (0, 1):
+                    for scale in (0.8, 6.0 / 7.0):
+                        t = f"{tag}: max_it={maxit} guess={guess} scale={scale}"
+                        k = solver(mA, maxit, scale, guess)
+                        _set(L, u, uv); _set(L, b, bv)
+                        L.KSPSolve(k, b, u)
+                        m1 = sweeps(A, d, uv if guess else np.zeros(nf), bv, maxit, scale)
+                        close(_get(L, u, nf), m1, f"{t}: KSPSolve")
+                        L.KSPBuildResidual(k, None, r, C.byref(V))
+                        L.VecNorm(V, NORM_2, C.byref(val))
+                        norm_close(val.value, bv - A @ m1, f"{t}: KSPBuildResidual + VecNorm")
+                        L.KSPSolve(k, b, u)                  # with a nonzero guess this adopts the sweeps the norm pass made
+                        m2 = sweeps(A, d, m1 if guess else np.zeros(nf), bv, maxit, scale)
+                        close(_get(L, u, nf), m2, f"{t}: the solve after the norm pass")
+                        close(_get(L, r, nf), bv - A @ m1, f"{t}: r of the norm pass")
+                        L.KSPDestroy(C.byref(k))
+            # a two-level step in the reference's order, v = (3, 3) and (2, 1)
+            for v0, v1, scale in ((3, 3, 0.8), (2, 1, 6.0 / 7.0)):
+                t = f"{tag}: two-level step v=({v0},{v1})"
+                k0, k1 = solver(mA, v0, scale, 1), solver(mAc, v1, scale, 0)
+                _set(L, u, uv); _set(L, b, bv)
+                L.KSPSolve(k0, b, u)
+                mu = sweeps(A, d, uv, bv, v0, scale)
+                L.KSPBuildResidual(k0, None, r, C.byref(V))
+                L.MatMult(mR, r, bc)
+                mbc = Rm @ (bv - A @ mu)
+                L.KSPSolve(k1, bc, uc)
+                muc = sweeps(Ac, dc, np.zeros(ncc), mbc, v1, scale)
+                L.MatMult(mP, uc, rv)
+                L.VecAXPY(u, 1.0, rv)
+                L.KSPSolve(k0, b, u)
+                mu = sweeps(A, d, mu + Pm @ muc, bv, v0, scale)
+                L.KSPBuildResidual(k0, None, r, C.byref(V))
+                L.VecNorm(V, NORM_2, C.byref(val))
+                norm_close(val.value, bv - A @ mu, f"{t}: norm")
+                close(_get(L, u, nf), mu, f"{t}: u")
+                close(_get(L, bc, ncc), mbc, f"{t}: coarse right-hand side")
+                close(_get(L, uc, ncc), muc, f"{t}: coarse solution")
+                close(_get(L, rv, nf), Pm @ muc, f"{t}: prolonged correction")
+                L.KSPDestroy(C.byref(k0)); L.KSPDestroy(C.byref(k1))
+            for v in (x, b, u, r, rv, y, uc, bc):
+                L.VecDestroy(C.byref(v))
+            L.MatDestroy(C.byref(mA)); L.MatDestroy(C.byref(mAc))
+        L.MatDestroy(C.byref(mR)); L.MatDestroy(C.byref(mP))
+
+
 if __name__ == "__main__":      # python tests/shim_semantics.py <shared library> <function name>: one check in a process of its own
     import os
     import sys
@@ -789,6 +970,7 @@ if __name__ == "__main__":      # python tests/shim_semantics.py <shared library
     lib = type_shim(C.CDLL(sys.argv[1], mode=os.RTLD_LOCAL))
     {"lazy": lazy_temporaries_keep_petsc_semantics, "spec": speculative_sweep_is_adopted_only_when_nothing_changed,
      "keepr": residual_left_deferred_by_the_norm_pass, "tailrec": recorded_coarse_subcycle_keeps_petsc_semantics, "pcmgtail": pcmg_level_vectors_after_the_tail_launch, "lu": richardson_with_lu_is_damped_not_exact,
+     "nonsym": nonsymmetric_operators_keep_petsc_semantics,
      "random": lambda L_, o_: random_programs_keep_petsc_semantics(L_, o_, seed=int(sys.argv[3]) if len(sys.argv) > 3 else 1,
                                                                    nprog=int(sys.argv[4]) if len(sys.argv) > 4 else 40)}[sys.argv[2]](lib, Oracle())
     print("SEMANTICS_OK", sys.argv[2])

@@ -65,6 +65,11 @@ def test_richardson_with_lu_is_damped_on_the_mock(mock_shim):
     _check(mock_shim, "lu")
 
 
+def test_nonsymmetric_operators_keep_petsc_semantics_on_the_mock(mock_shim):
+    """five distinct coefficients / row tables with W != E through MatSetValue: recognised, and every value that of dense numpy"""
+    _check(mock_shim, "nonsym")
+
+
 def test_random_programs_of_petsc_calls_keep_petsc_semantics_on_the_mock(mock_shim):
     """random_programs_keep_petsc_semantics: 25 programs of up to 60 calls (seed 1); round 3 ran 7 seeds x 40 programs over the mock: no deviation"""
     _check(mock_shim, "random", "1", "25")
