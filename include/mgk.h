@@ -525,6 +525,29 @@ int  mgk_flag_wait(mgk_ctx *ctx, const void *flag, unsigned long long value, dou
 int  mgk_peer_allreduce(mgk_ctx *ctx, void *const *peer_blocks, int nranks, int me, unsigned long long seq, double *vals_dev, int n,
                         double timeout_s, void *status_u32, void *stream);
 
+/* ---- Krylov orthogonalisation (restarted GMRES of the own driver, csrc/mg_gmres.c; kernels in csrc/mgk_krylov.hip) ----
+ * Level fields in the padded layout, fp64, no FMA; sums run over interior points only and nothing outside the interior of an output is
+ * written.  v = k device fields (host array of device pointers), 1 <= k <= MGK_KRYLOV_MAX.  Reductions are deterministic (per-block
+ * partials, fixed-order finish).  The reduced values land in device memory AND, by a stream-ordered copy, in the context's pinned landing
+ * area; a non-NULL *_host argument synchronises the stream and returns them at once, NULL leaves them for mgk_krylov_fetch: the two passes
+ * of an Arnoldi step run back to back and the host waits once.
+ *   mgk_multi_dot_f64          out_dev[i] = v_i . w for i < k, ONE pass that reads w once                    (8k + 8) B per unknown
+ *   mgk_multi_axpy_sumsq_f64   w <- (..((w - h[0] v_0) - h[1] v_1)..) - h[k-1] v_{k-1} (ascending i, multiply and subtract rounded separately;
+ *                              h is read from DEVICE memory, e.g. where mgk_multi_dot_f64 left it) and the sum of squares of the new w (8k + 16) B
+ *   mgk_krylov_fetch           waits for `stream`, then h_host[0..k-1] = the last multi-dot's values, *sumsq_host = the last multi-axpy's
+ *   mgk_lincomb_f64            out = (..(y[0] v_0 + y[1] v_1)..) + y[k-1] v_{k-1} (y on the host; the first product starts the sum)
+ *   mgk_scale_to_f64           out = a x, and out2 = a x as well unless out2 is NULL
+ * Stores are ordinary for fields within the 256 MB Infinity Cache and non-temporal above (every pass reads what the launch before it wrote);
+ * mgk_set_tuning(variant = 0 / 1) forces the ordinary / the non-temporal form. */
+#define MGK_KRYLOV_MAX 33
+int  mgk_multi_dot_f64(mgk_ctx *ctx, const mgk_geom *g, int k, const double *const *v, const double *w, double *out_dev, double *out_host,
+                       void *stream);
+int  mgk_multi_axpy_sumsq_f64(mgk_ctx *ctx, const mgk_geom *g, int k, const double *h_dev, const double *const *v, double *w,
+                              double *sumsq_host, void *stream);
+int  mgk_krylov_fetch(mgk_ctx *ctx, int k, double *h_host, double *sumsq_host, void *stream);
+int  mgk_lincomb_f64(mgk_ctx *ctx, const mgk_geom *g, int k, const double *y, const double *const *v, double *out, void *stream);
+int  mgk_scale_to_f64(mgk_ctx *ctx, const mgk_geom *g, double a, const double *x, double *out, double *out2, void *stream);
+
 /* tuning knob for the marching stencil kernel (profiling only): <=0 keeps the built-in choice */
 void mgk_set_tuning(int variant, int zchunk);
 

@@ -108,6 +108,19 @@ int  mg_solver_cycles(mg_solver *s, int ncycles);
 int  mg_solver_fmg(mg_solver *s, int nu);
 /* FMG(nu), then V-cycles under the stop rule of mg_solver_solve; solve_seconds covers both */
 int  mg_solver_solve_fmg(mg_solver *s, int nu);
+/* Restarted GMRES(restart) with the V-cycle as right preconditioner (PETSc's -ksp_type gmres -pc_type mg -ksp_pc_side right) on the current
+ * right-hand side, classical Gram-Schmidt without refinement.  M = one V-cycle from the zero guess, A = the fine-level operator:
+ *   x = 0, r = b, beta = ||b||, v_0 = r / beta;
+ *   step j: z = M v_j, w = A z, h_i = v_i . w (i <= j), w -= sum h_i v_i, h_{j+1} = ||w||, Givens rotations give the estimate |g_{j+1}| of
+ *           ||b - A x_j||, v_{j+1} = w / h_{j+1};
+ *   at a stop or after `restart` steps: H y = g, x += M (V y); going on from r = b - A x, beta = ||r||.
+ * Stops when the estimate is <= rtol ||b||, after maxiter steps, or under the divergence guard of mg_solver_solve; h_{j+1} = 0 ends it as
+ * converged.  On return: the solution is x, level 0's right-hand side is the caller's, iterations = Arnoldi steps (= applications of M
+ * less one per restart cycle), rnorm[0] = ||b||, rnorm[k] = the estimate after step k, solve_seconds covers the call; reset + solve
+ * then behave as on a fresh solver.  The first call for a restart length allocates restart + 4 fine-level fields (freed by
+ * mg_solver_destroy); if they do not fit the error names the restart length and the bytes and nothing stays allocated.
+ * One GPU, fp64, Richardson + Jacobi, any mesh, 2-D and 3-D, 1 <= restart <= MGK_KRYLOV_MAX - 1: anything else returns MGK_EINVAL. */
+int  mg_solver_solve_gmres(mg_solver *s, int restart);
 /* block until every stream of this solver's device is idle */
 int  mg_solver_sync(mg_solver *s);
 

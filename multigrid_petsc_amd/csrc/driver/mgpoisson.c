@@ -4,10 +4,13 @@
  *
  *   mgpoisson [-dim 2|3] [-npts N] [-levels L] [-iter M] [-v v0,v1] [-ksp_type richardson|chebyshev]
  *             [-ksp_richardson_scale s] [-ksp_chebyshev_eigenvalues emin,emax] [-precision fp64|mixed]
- *             [-device d] [-options_file poisson.in] [-write_fields 0|1]
+ *             [-device d] [-options_file poisson.in] [-write_fields 0|1] [-mg_accel gmres [-mg_gmres_restart m]]
  *
  * Same option spelling as the reference where it has one (-npts -levels -iter -v; poisson.in syntax: '#'
  * comments, "-key value" lines); -grids is implied (= -levels: one grid per level), -cycle is 0; -mesh 0|1|2 (1, 2: 2-D).
+ * -mg_accel gmres: restarted GMRES with the V-cycle as right preconditioner (PETSc's -ksp_type gmres -pc_type mg) instead of the plain
+ * iteration, -mg_gmres_restart m (default 30, PETSc's) its restart length; "Number of iterations" then counts Arnoldi steps and rData.dat
+ * holds the residual estimates.  Without the option nothing changes.
  * Output mirrors what the reference prints: the PrintInfo block (src/poisson.c:165-214), error[0..2]
  * (src/solver.c:1333), "Relative residual" (:1354), "Solver walltime" (:1572), and the five files of
  * Postprocessing (src/solver.c:160-164,1331-1353): eData.dat, rData.dat, and -- the O(N) text dumps --
@@ -21,6 +24,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
+
+/* a driver linked without csrc/mg_gmres.c (the host tests link this file with mg_solver.c alone) still links: -mg_accel gmres is then refused */
+extern int mg_solver_solve_gmres(mg_solver *s, int restart) __attribute__((weak));
 
 typedef struct { char key[64], val[128]; } kv;
 static kv g_kv[128];
@@ -86,13 +92,21 @@ int main(int argc, char **argv) {
         fprintf(stderr, "mgpoisson: -grids %d differs from -levels %d: only one grid per level (the V-cycle case) is built\n", atoi(v), c.levels);
         return 2;
     }
+    int gmres = 0, restart = 30;                       /* -mg_accel gmres: mg_solver_solve_gmres instead of mg_solver_solve */
+    if ((v = get("-mg_accel"))) {
+        if (!strcmp(v, "gmres")) gmres = 1;
+        else if (strcmp(v, "none")) { fprintf(stderr, "mgpoisson: -mg_accel must be gmres or none\n"); return 2; }
+    }
+    if ((v = get("-mg_gmres_restart"))) restart = atoi(v);
+    if (gmres && !mg_solver_solve_gmres) { fprintf(stderr, "mgpoisson: this build has no GMRES (-mg_accel gmres)\n"); return 2; }
+    if (gmres && (restart < 1 || restart > MGK_KRYLOV_MAX - 1)) { fprintf(stderr, "mgpoisson: -mg_gmres_restart must be within 1 .. %d\n", MGK_KRYLOV_MAX - 1); return 2; }
     int map = 2;                                       /* poisson.in:11 */
     if ((v = get("-map"))) map = atoi(v);
     if (map < 0 || map > 2) { fprintf(stderr, "mgpoisson: -map must be 0, 1 or 2 (src/poisson.c:190-192)\n"); return 2; }
 
     mg_solver *s = NULL;
     if (mg_solver_create(&s, &c, NULL)) { fprintf(stderr, "mgpoisson: %s\n", mg_last_error()); return 1; }
-    if (mg_solver_set_rhs_problem(s) || mg_solver_solve(s)) { fprintf(stderr, "mgpoisson: %s\n", mg_last_error()); return 1; }
+    if (mg_solver_set_rhs_problem(s) || (gmres ? mg_solver_solve_gmres(s, restart) : mg_solver_solve(s))) { fprintf(stderr, "mgpoisson: %s\n", mg_last_error()); return 1; }
     const int it = mg_solver_iterations(s);
     const double *rn = mg_solver_rnorm(s);
     double err[3];

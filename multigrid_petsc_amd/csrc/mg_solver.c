@@ -442,6 +442,8 @@ void mg_solver_destroy(mg_solver *s) {
         for (int q = 0; q < s->ntimers_created; q++) mgk_timer_destroy(s->ctx, s->timers[q]);
         if (s->d_norms) mgk_free(s->ctx, s->d_norms);
         if (s->pin) mgk_host_free(s->ctx, s->pin);
+        for (int q = 0; q < s->gm_nfields; q++) if (s->gm_field[q]) mgk_free(s->ctx, s->gm_field[q]);
+        if (s->gm_hdev) mgk_free(s->ctx, s->gm_hdev);
         for (int p = 0; p < 2; p++) if (s->coarse_graph[p]) mgk_graph_destroy(s->ctx, s->coarse_graph[p]);
         for (int l = 0; l < s->levels; l++) {
             mg_level *L = &s->L[l];
@@ -1563,6 +1565,12 @@ norm_done:
     return 0;
 }
 
+/* every per-level flag back to its state before the first cycle */
+static void reset_level_flags(mg_solver *s) {
+    for (int l = 0; l < s->levels; l++)
+        for (int p = 0; p < 2; p++) { s->L[l].f[p].guess_nonzero = 0; s->L[l].f[p].u_ghost_ok = 0; s->L[l].f[p].u_ghost_pending = 0; s->L[l].f[p].b_ghost_ok = 0; s->L[l].f[p].jz_ready = 0; s->L[l].f[p].last_sweep_pending = 0; s->L[l].f[p].bfar_ok = 0; s->L[l].f[p].pre_done = 0; }
+}
+
 /* src/solver.c:1512-1523 */
 static int start(mg_solver *s) {
     mg_level *L = &s->L[0];
@@ -1570,8 +1578,7 @@ static int start(mg_solver *s) {
     double ss;
     CHK(mgk_sumsq_f64(s->ctx, &F->g, (const double *)F->b, &ss, NULL)); /* VecNorm(b[0]) :1512 */
     CHK(norm_from_sumsq(s, ss, &s->bnorm));
-    for (int l = 0; l < s->levels; l++)
-        for (int p = 0; p < 2; p++) { s->L[l].f[p].guess_nonzero = 0; s->L[l].f[p].u_ghost_ok = 0; s->L[l].f[p].u_ghost_pending = 0; s->L[l].f[p].b_ghost_ok = 0; s->L[l].f[p].jz_ready = 0; s->L[l].f[p].last_sweep_pending = 0; s->L[l].f[p].bfar_ok = 0; s->L[l].f[p].pre_done = 0; }
+    reset_level_flags(s);
     CHK(mgk_memset0(s->ctx, F->u, sizeof(double) * (size_t)F->g.total, NULL));   /* VecSet(u[0],0) :1514 */
     /* rv = A u - b with u = 0 (:1516-1517); ||A u - b|| = ||b - A u||, evaluated by the same residual kernel */
     if (s->cfg.precision == MG_PREC_MIXED)
@@ -1705,6 +1712,18 @@ int mgi_start(mg_solver *s) { return start(s); }
 int mgi_smooth(mg_solver *s, int l, int maxit) { return smooth(s, 0, l, maxit, 0); }
 int mgi_vcycle_once(mg_solver *s) { return vcycle_once(s); }
 int mgi_finalize(mg_solver *s) { return finalize_iterate(s); }
+
+/* u_0 = (one cycle from the zero guess)(b_0): cycle_body as the first iteration of a solve runs it, told that nothing follows -- so the
+ * post-smoothing is complete (fuse bit 12 owes no sweep) and no speculative sweep is made.  Level 0 swaps u / tmp as often as in any other
+ * cycle: the coarse-level graph's recording stays valid */
+int mgi_apply_cycle(mg_solver *s) {
+    reset_level_flags(s);
+    s->spec_valid = 0; s->sweep_owed = 0; s->iterate_behind = 0;
+    s->last_cycle = 1;
+    int rc = cycle_body(s, 0, 1);
+    s->last_cycle = 0;
+    return rc;
+}
 
 /* one iteration of the reference's loop (src/solver.c:1531-1543) on the levels l .. L-1 alone, level l in the role of level 0: v0 sweeps on
  * l from the guess in u_l (its KSP keeps the non-zero guess), the descent and the ascent as in cycle_body -- the tail kernel when l lies

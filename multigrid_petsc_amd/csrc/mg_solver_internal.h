@@ -1,7 +1,8 @@
 /*
- * mg_solver_internal.h -- the solver's state and the cycle steps that the full-multigrid driver (mg_fmg.c) builds on.  Private to
- * libmgpetsc.so: not installed, not part of the C API (include/mgsolve.h).  Everything declared here is DEFINED in mg_solver.c, which
- * references no symbol of mg_fmg.c (the host tests link mg_solver.c without it, against a mock of the kernel ABI).
+ * mg_solver_internal.h -- the solver's state and the cycle steps that the full-multigrid driver (mg_fmg.c) and the GMRES driver (mg_gmres.c)
+ * build on.  Private to libmgpetsc.so: not installed, not part of the C API (include/mgsolve.h).  Everything declared here is DEFINED in
+ * mg_solver.c, which references no symbol of mg_fmg.c or mg_gmres.c (the host tests link mg_solver.c without them, against a mock of the
+ * kernel ABI).
  */
 #ifndef MG_SOLVER_INTERNAL_H
 #define MG_SOLVER_INTERNAL_H
@@ -78,6 +79,11 @@ struct mg_solver {
     unsigned char timer_kind[MG_MAX_TIMERS];
     int prof_kind;          /* kind of the next timer: 0 plain sweep, 1 two sweeps in one pass */
     int ntimers_created;
+    /* GMRES (mg_gmres.c): fine-level fields allocated at the first mg_solver_solve_gmres for a restart length -- basis (restart + 1), x, w, the
+     * caller's b -- and the device slots of the Hessenberg column; freed by mg_solver_destroy */
+    void *gm_field[MGK_KRYLOV_MAX + 3];
+    int gm_nfields, gm_restart;
+    double *gm_hdev;
 };
 
 /* KSPCHEBYSHEV on the fused cycle (fuse bit 15): mg_cheby.c holds the only calls of the mgk_cheby3_2d_* / mgk_tail_cycle_cheby_f64 kernels.
@@ -98,4 +104,8 @@ int    mgi_vcycle_rooted(mg_solver *s, int l);           /* one V-cycle on the l
 int    mgi_vcycle_once(mg_solver *s);                    /* one iteration of the solve loop (cycle rooted at level 0 + the norm), iter += 1 */
 int    mgi_iterate(mg_solver *s);                        /* the solve loop under the stop rule of src/solver.c:1530, from the current state */
 int    mgi_finalize(mg_solver *s);                       /* materialise the iterate the last norm belongs to */
+/* the V-cycle as a linear operator (mg_gmres.c): ONE cycle rooted at level 0 from the zero guess on whatever level 0's b holds, no norm; the
+ * complete iterate lands in level 0's u (no sweep stays owed).  Every flag is reset as mgi_start does; the coarse-level graph and the LDS tail
+ * are used */
+int    mgi_apply_cycle(mg_solver *s);
 #endif

@@ -17,8 +17,8 @@ struct mgk_ctx {
     int device;
     hipStream_t compute, comm;
     double *partials;      // reduction scratch (device)
-    double *result_dev;    // 8 doubles (device)
-    double *result_host;   // 8 doubles (pinned host)
+    double *result_dev;    // MGK_RESULT_SLOTS doubles (device)
+    double *result_host;   // MGK_RESULT_SLOTS doubles (pinned host): the landing area of reduced values
     int max_partials;
     hipEvent_t ev[32];     // ring of dependency events for mgk_stream_wait (no create/destroy on the hot path)
     int ev_next;
@@ -34,6 +34,8 @@ typedef double __attribute__((address_space(4))) CDBL4;
 extern thread_local int g_variant, g_zchunk;
 int finish_to_host(mgk_ctx *c, int nparts, int nslots, hipStream_t s, double *host_out);
 int mgk_preload_kernels3();      // forces the code object of mgk_kernels3.hip to load (mgk_ctx_create)
+int mgk_preload_krylov();        // ... and that of mgk_krylov.hip
+#define MGK_RESULT_SLOTS 64      // >= MGK_KRYLOV_MAX + 1: the dots of an Arnoldi step and the norm that follows them
 
 // ------------------------------------------------------------------------------------------
 // device helpers

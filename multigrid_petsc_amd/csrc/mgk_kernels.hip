@@ -61,8 +61,8 @@ extern "C" int mgk_ctx_create(mgk_ctx **out, int device) {
     c->chunk_planes = 0;
     c->max_partials = 16384;
     HIPCHK(hipMalloc(&c->partials, sizeof(double) * 3 * c->max_partials));
-    HIPCHK(hipMalloc(&c->result_dev, sizeof(double) * 8));
-    HIPCHK(hipHostMalloc(&c->result_host, sizeof(double) * 8, hipHostMallocDefault));
+    HIPCHK(hipMalloc(&c->result_dev, sizeof(double) * MGK_RESULT_SLOTS));
+    HIPCHK(hipHostMalloc(&c->result_host, sizeof(double) * MGK_RESULT_SLOTS, hipHostMallocDefault));
     for (int q = 0; q < 32; q++) HIPCHK(hipEventCreateWithFlags(&c->ev[q], hipEventDisableTiming));
     c->ev_next = 0;
     {   // HIP loads a translation unit's code object at the first use of one of its kernels (~2 ms each: a third of the reference driver's
@@ -70,6 +70,7 @@ extern "C" int mgk_ctx_create(mgk_ctx **out, int device) {
         hipFuncAttributes fa;
         HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_finish_sum)));
         int rc = mgk_preload_kernels3();
+        if (!rc) rc = mgk_preload_krylov();
         if (rc) return rc;
     }
     *out = c;

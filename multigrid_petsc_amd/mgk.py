@@ -166,6 +166,12 @@ def _sigs(L):
         "mgk_d2h_async": (i, [vp, vp, vp, sz, vp]),
         "mgk_h2d_async": (i, [vp, vp, vp, sz, vp]),
         "mgk_delay_us": (i, [vp, d, vp]),
+        # Krylov orthogonalisation: v = array of k device pointers
+        "mgk_multi_dot_f64": (i, [vp, G, i, C.POINTER(vp), vp, vp, c_dp, vp]),
+        "mgk_multi_axpy_sumsq_f64": (i, [vp, G, i, vp, C.POINTER(vp), vp, C.POINTER(d), vp]),
+        "mgk_krylov_fetch": (i, [vp, i, c_dp, C.POINTER(d), vp]),
+        "mgk_lincomb_f64": (i, [vp, G, i, c_dp, C.POINTER(vp), vp, vp]),
+        "mgk_scale_to_f64": (i, [vp, G, d, vp, vp, vp, vp]),
         "mgk_paced_copy": (i, [vp, vp, vp, sz, d, i, vp]),
     }
     for name, (res, args) in S.items():

@@ -93,6 +93,15 @@ def _fmg_lib(L):
     return L
 
 
+def _gmres_lib(L):
+    """the GMRES entry point, bound on first use like the full-multigrid ones"""
+    if not getattr(L, "_mg_gmres_sigs", False):
+        L.mg_solver_solve_gmres.restype = C.c_int
+        L.mg_solver_solve_gmres.argtypes = [C.c_void_p, C.c_int]
+        L._mg_gmres_sigs = True
+    return L
+
+
 def get_ranges(totaln, procs):
     r = np.zeros(procs + 1, dtype=np.int32)
     _lib().mg_get_ranges(totaln, procs, r.ctypes.data_as(C.c_void_p))
@@ -168,6 +177,12 @@ class Solver:
     def solve_fmg(self, nu=1):
         """FMG(nu), then V-cycles under solve()'s stop rule; returns the iteration count (FMG included)"""
         self._chk(_fmg_lib(self.L).mg_solver_solve_fmg(self.h, nu))
+        return self.iterations
+
+    def solve_gmres(self, restart=30):
+        """restarted GMRES(restart) with the V-cycle as right preconditioner (PETSc's -ksp_type gmres -pc_type mg); returns the number of
+        Arnoldi steps; rnorm[k] is the residual estimate after step k"""
+        self._chk(_gmres_lib(self.L).mg_solver_solve_gmres(self.h, restart))
         return self.iterations
 
     def sync(self):
