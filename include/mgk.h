@@ -548,7 +548,27 @@ int  mgk_krylov_fetch(mgk_ctx *ctx, int k, double *h_host, double *sumsq_host, v
 int  mgk_lincomb_f64(mgk_ctx *ctx, const mgk_geom *g, int k, const double *y, const double *const *v, double *out, void *stream);
 int  mgk_scale_to_f64(mgk_ctx *ctx, const mgk_geom *g, double a, const double *x, double *out, double *out2, void *stream);
 
-/* tuning knob for the marching stencil kernel (profiling only): <=0 keeps the built-in choice */
+/* ---- y-line Jacobi on the 2-D row-table operators (csrc/mg_line.c; kernels in csrc/mgk_line.hip) ----
+ * One sweep u <- u + scale T^-1 (b - A u), T = the y-tridiagonal part of A, in two passes.  The coefficients depend on the grid row only, so
+ * the factorisation of T is the same in every column: per-row device tables (ny doubles each), in C99 double without FMA
+ *   m_0 = C_0, g_0 = 1/m_0, l_0 = 0;  i >= 1: l_i = S_i g_{i-1}, m_i = C_i - l_i N_{i-1}, g_i = 1/m_i;  q_i = N_i g_i
+ * with {S, W, C, E, N}_i = atab[5 i + 0..4]: atab is the level's row table, the ctab of the *_rowcoef_* entry points (ny x 5).
+ *   mgk_line_forward_f64    r_i = b_i - (A u)_i (the five terms in the order of mgk_rowcoef_f64 mode 1); y_0 = r_0, y_i = r_i - l_i y_{i-1};
+ *                           z_i = y_i g_i.  u == NULL: the zero guess, r = b, atab is not needed.  z must not alias b or u.   24 (16) B per unknown
+ *   mgk_line_backward_f64   e_{n-1} = z_{n-1}, e_i = z_i - q_i e_{i+1};  unew_i = u_i + scale e_i; u == NULL: the zero guess, unew_i = scale e_i.
+ *                           unew may be u itself (a point reads only itself): a sweep swaps no buffers.                24 (16) B per unknown
+ * Multiply and subtract are rounded separately; nothing outside the interior of an output is written.  The pitch may be at most 2^21 doubles
+ * (rows are addressed by 32-bit byte offsets inside a window of 67 rows; MGK_EINVAL beyond).  Stores: as the Krylov passes below
+ * (by size).  They share the per-thread knobs of mgk_set_tuning with every other kernel that reads them: variant = 0 / 1 forces one store
+ * policy, and the second argument, > 0, is the depth of the prefetch ring in rows (rounded down to a built one: 8, 16, 32). */
+int  mgk_line_forward_f64(mgk_ctx *ctx, const mgk_geom *g, const double *atab, const double *ltab, const double *gtab,
+                          const double *b, const double *u, double *z, void *stream);
+int  mgk_line_backward_f64(mgk_ctx *ctx, const mgk_geom *g, const double *qtab, double scale, const double *z, const double *u,
+                           double *unew, void *stream);
+
+/* tuning knobs (profiling only), per calling thread: <=0 keeps the built-in choice.  They are GLOBAL to that thread, not per kernel: the
+ * marching stencil kernels read (variant, z chunk), the Krylov passes and the two line kernels read variant = 0 / 1 as their store policy,
+ * and the line kernels read the second argument as their prefetch depth in rows -- set them back to (-1, -1) after measuring one kernel. */
 void mgk_set_tuning(int variant, int zchunk);
 
 #ifdef __cplusplus

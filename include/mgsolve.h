@@ -20,6 +20,7 @@ extern "C" {
 
 typedef enum { MG_KSP_RICHARDSON = 0, MG_KSP_CHEBYSHEV = 1 } mg_ksp_type;
 typedef enum { MG_PREC_FP64 = 0, MG_PREC_MIXED = 1 } mg_precision;
+typedef enum { MG_PC_JACOBI = 0, MG_PC_LINE_Y = 1 } mg_pc_type;
 
 /* options of the reference driver (src/poisson.c:51-59, poisson.in) + the PETSc options that
  * KSPSetFromOptions (src/solver.c:1476,1492,1509) would pick up for the smoother */
@@ -78,6 +79,14 @@ typedef struct mg_config {
     int mesh;           /* -mesh: 0 uniform; 1 / 2: the reference's meshes stretched in y (src/mesh.c:45-107,165-169), 2-D, one GPU,
                          * Richardson + Jacobi: the operator rows then depend on the grid row (per-row coefficient tables); the same
                          * fused cycle on the row-table forms of its kernels (mgk_*_rowcoef_f64) */
+    int pc_type;        /* -pc_type: MG_PC_JACOBI (0, default) point Jacobi; MG_PC_LINE_Y (1) y-line Jacobi: one sweep is u <- u + scale T^-1 (b - A u)
+                         * with T the y-tridiagonal part of A, solved exactly in every column (Thomas; the factorisation is the same in every
+                         * column, three tables per level made at creation) by a forward and a backward pass (mgk_line_forward_f64 /
+                         * mgk_line_backward_f64).  The remedy for the cells of -mesh 1 that are thin in y, where point Jacobi stops smoothing:
+                         * the cycle count no longer grows with npts.  2-D, fp64, one rank, Richardson, meshes 0 / 1 / 2, any v and scale;
+                         * anything else is refused by mg_solver_create with MGK_EINVAL, and so are mg_solver_fmg*, mg_solver_solve_gmres on
+                         * such a solver.  The fuse bits that bake point Jacobi into a pass (1, 3, 5, 8-15) are cleared; bits 0 and 2 stay,
+                         * the coarse levels run by launch inside the HIP graph (a line sweep swaps no buffers) */
 } mg_config;
 
 void mg_config_default(mg_config *cfg);     /* poisson.in defaults + -pc_type jacobi -ksp_richardson_scale 1 */
@@ -104,7 +113,7 @@ int  mg_solver_cycles(mg_solver *s, int ncycles);
 /* full multigrid FMG(nu) (PETSc's -pc_mg_type full) on the current right-hand side: b_l = R b_{l-1} down the levels, v1 sweeps from the
  * zero guess on the coarsest, then on each finer level l: u_l = 0 + P u_{l+1} and nu V-cycles on the levels l .. L-1 from that guess.
  * Leaves the solver as one iteration would (rnorm[0] = ||b||, rnorm[1] = ||b - A u0||, iterations = 1); mg_solver_cycles continues
- * with V-cycles from u0.  One GPU, fp64, Richardson + Jacobi, uniform mesh, levels >= 2, nu >= 1: anything else returns MGK_EINVAL. */
+ * with V-cycles from u0.  One GPU, fp64, Richardson + point Jacobi, uniform mesh, levels >= 2, nu >= 1: anything else returns MGK_EINVAL. */
 int  mg_solver_fmg(mg_solver *s, int nu);
 /* FMG(nu), then V-cycles under the stop rule of mg_solver_solve; solve_seconds covers both */
 int  mg_solver_solve_fmg(mg_solver *s, int nu);
@@ -119,7 +128,7 @@ int  mg_solver_solve_fmg(mg_solver *s, int nu);
  * less one per restart cycle), rnorm[0] = ||b||, rnorm[k] = the estimate after step k, solve_seconds covers the call; reset + solve
  * then behave as on a fresh solver.  The first call for a restart length allocates restart + 4 fine-level fields (freed by
  * mg_solver_destroy); if they do not fit the error names the restart length and the bytes and nothing stays allocated.
- * One GPU, fp64, Richardson + Jacobi, any mesh, 2-D and 3-D, 1 <= restart <= MGK_KRYLOV_MAX - 1: anything else returns MGK_EINVAL. */
+ * One GPU, fp64, Richardson + point Jacobi, any mesh, 2-D and 3-D, 1 <= restart <= MGK_KRYLOV_MAX - 1: anything else returns MGK_EINVAL. */
 int  mg_solver_solve_gmres(mg_solver *s, int restart);
 /* block until every stream of this solver's device is idle */
 int  mg_solver_sync(mg_solver *s);

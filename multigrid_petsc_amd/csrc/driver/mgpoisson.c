@@ -84,7 +84,8 @@ int main(int argc, char **argv) {
     if ((v = get("-mg_fuse"))) c.fuse = atoi(v);                    /* tuning / testing: mg_config.fuse, .pair_min_n, .graph */
     if ((v = get("-mg_pair_min_n"))) c.pair_min_n = atoi(v);
     if ((v = get("-mg_graph"))) c.graph = atoi(v);
-    if ((v = get("-pc_type")) && strcmp(v, "jacobi")) { fprintf(stderr, "mgpoisson: only -pc_type jacobi is built\n"); return 2; }
+    if ((v = get("-pc_type")) && !strcmp(v, "yline")) c.pc_type = MG_PC_LINE_Y;     /* y-line Jacobi (2-D; the remedy for -mesh 1) */
+    else if (v && strcmp(v, "jacobi")) { fprintf(stderr, "mgpoisson: only -pc_type jacobi and -pc_type yline are built\n"); return 2; }
     if ((v = get("-cycle")) && atoi(v) != 0) { fprintf(stderr, "mgpoisson: only -cycle 0 (V-cycle) is built\n"); return 2; }
     if ((v = get("-mesh"))) c.mesh = atoi(v);
     /* the V-cycle has one grid per level (src/poisson.c:61-71 guards the other combinations): -grids, when given, must agree */

@@ -292,6 +292,15 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
     if (cfg->dim != 2 && cfg->dim != 3) return mgfail(MGK_EINVAL, "mg_solver_create: dim must be 2 or 3");
     if (cfg->levels < 1 || cfg->levels > MG_MAX_LEVELS) return mgfail(MGK_EINVAL, "mg_solver_create: bad level count");
     if (cfg->npts < 3) return mgfail(MGK_EINVAL, "mg_solver_create: npts < 3");
+    if (cfg->pc_type != MG_PC_JACOBI && cfg->pc_type != MG_PC_LINE_Y) return mgfail(MGK_EINVAL, "mg_solver_create: pc_type must be jacobi (0) or yline (1)");
+    if (cfg->pc_type == MG_PC_LINE_Y) {
+        /* y-line Jacobi (mg_line.c): 2-D, fp64, one rank, Richardson */
+        if (cfg->dim != 2) return mgfail(MGK_EINVAL, "mg_solver_create: the y-line smoother is built for 2-D (not 3-D: that needs a plane smoother)");
+        if (cfg->precision != MG_PREC_FP64) return mgfail(MGK_EINVAL, "mg_solver_create: the y-line smoother is built for fp64 (not mixed precision)");
+        if (cfg->ksp_type != MG_KSP_RICHARDSON) return mgfail(MGK_EINVAL, "mg_solver_create: the y-line smoother is built for Richardson (not Chebyshev)");
+        if (cfg->nranks > 1) return mgfail(MGK_EINVAL, "mg_solver_create: the y-line smoother is built for one GPU (nranks == 1)");
+        if (!mg_line_tables || !mg_line_smooth) return mgfail(MGK_EINVAL, "mg_solver_create: this build has no y-line smoother (mg_line.c is not linked)");
+    }
     if (cfg->precision == MG_PREC_MIXED && (cfg->dim != 3 || cfg->ksp_type != MG_KSP_RICHARDSON))
         return mgfail(MGK_EINVAL, "mg_solver_create: mixed precision is built for 3-D, Richardson+Jacobi");
     /* npts-1 must be divisible by 2^(levels-1) and the coarsest grid must keep >= 1 unknown */
@@ -318,6 +327,9 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
     if (s->cfg.fuse < 0) s->cfg.fuse = 63 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768;
     if (s->cfg.pair_min_n <= 0) s->cfg.pair_min_n = (cfg->dim == 3) ? 255 : 2047;   /* where a two-sweep pass beats two sweeps
                                                                                       * (255^3: 0.107 ms against 2 x 0.063) */
+    /* y-line Jacobi: the passes that bake point Jacobi in are off (bits 1, 3, 5, 8-15); the fused residual + norm (0) and residual +
+     * restriction (2) stay, the coarse levels run by launch inside the HIP graph */
+    if (s->cfg.pc_type == MG_PC_LINE_Y) s->cfg.fuse &= ~(2 | 8 | 32 | 0xff00);
     if (s->cfg.mesh) s->cfg.fuse &= ~(16 | 128);   /* row-dependent coefficients (2-D, fp64): the same fused cycle on the row-table forms of the kernels */
     if (s->cfg.overlap < 0) s->cfg.overlap = 1;
     if (s->cfg.graph < 0) s->cfg.graph = 1;
@@ -375,11 +387,16 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         if (rc) { mg_solver_destroy(s); return mgfail(rc, "mg_solver_create: geometry"); }
         level_stencil(cfg->dim, L->n, L->coef, &L->h);
         L->dinv = 1.0 / L->coef[cfg->dim == 3 ? 3 : 2];      /* PCJACOBI: 1/diag(A) */
-        if (cfg->mesh) {
+        if (cfg->mesh || cfg->pc_type == MG_PC_LINE_Y) {
             double *hc = (double *)malloc(sizeof(double) * 5 * (size_t)L->n), *hd = (double *)malloc(sizeof(double) * (size_t)L->n);
-            level_row_tables(cfg->npts, cfg->mesh, l, L->n, hc, hd);
+            if (cfg->mesh) level_row_tables(cfg->npts, cfg->mesh, l, L->n, hc, hd);
+            else for (int i = 0; i < L->n; i++) {           /* uniform mesh: the level's five constants in every row */
+                for (int e = 0; e < 5; e++) hc[5 * (size_t)i + e] = L->coef[e];
+                hd[i] = L->dinv;
+            }
             rc = upload(s, hc, 5 * (size_t)L->n, &L->ctab);
             if (!rc) rc = upload(s, hd, (size_t)L->n, &L->dtab);
+            if (!rc && cfg->pc_type == MG_PC_LINE_Y) rc = mg_line_tables(s, l, hc);
             free(hc); free(hd);
             if (rc) { mg_solver_destroy(s); return mgfail(rc, "mg_solver_create: coefficient tables"); }
         }
@@ -454,6 +471,9 @@ void mg_solver_destroy(mg_solver *s) {
             if (L->p2) mgk_free(s->ctx, L->p2);
             if (L->ctab) mgk_free(s->ctx, L->ctab);
             if (L->dtab) mgk_free(s->ctx, L->dtab);
+            if (L->ltab) mgk_free(s->ctx, L->ltab);
+            if (L->gtab) mgk_free(s->ctx, L->gtab);
+            if (L->qtab) mgk_free(s->ctx, L->qtab);
         }
         mgk_ctx_destroy(s->ctx);
     }
@@ -771,6 +791,12 @@ static int triple_ok(const mg_solver *s, int P, int l, int maxit) {
 
 /* pre: pre-smoothing, a restriction from this level follows (src/solver.c:1531 / :1536 before :1534 of the next level) */
 static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
+    if (s->cfg.pc_type == MG_PC_LINE_Y) {                           /* y-line Jacobi: every sweep in place (mg_line.c), no swap, no flag */
+        mg_fset *Fl = &s->L[l].f[0];
+        Fl->pre_done = 0; Fl->jz_ready = 0; Fl->last_sweep_pending = 0;
+        Fl->u_ghost_ok = 0; Fl->u_ghost_pending = 0;
+        return mg_line_smooth(s, l, maxit);
+    }
     if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV && !j3_2d_ok(s, P, l, maxit)) return smooth_chebyshev(s, l, maxit);
     mg_level *L = &s->L[l];
     mg_fset *F = &L->f[P];
@@ -1344,7 +1370,7 @@ gathered:
 static int coarse_part(mg_solver *s, int P, int lg) {
     const int levels = s->levels, lend = s->ltail ? s->ltail : levels - 1;     /* last level the loops below handle themselves */
     for (int l = lg; l <= lend; l++) CHK(descend(s, P, l));
-    if (!s->ltail && (s->cfg.v[1] & 1)) {                               /* restore the coarsest level's buffer identity */
+    if (!s->ltail && (s->cfg.v[1] & 1) && s->cfg.pc_type != MG_PC_LINE_Y) {   /* restore the coarsest level's buffer identity (a line sweep swaps nothing) */
         mg_fset *Cz = &s->L[levels - 1].f[P];
         CHK(mgk_d2d(s->ctx, Cz->tmp, Cz->u, (size_t)OPS[P].esz * (size_t)Cz->g.total, NULL));
         swap_ptr(&Cz->u, &Cz->tmp);
@@ -1707,6 +1733,7 @@ double mg_solver_dof_updates_per_cycle(const mg_solver *s) {
 /* steps for the full-multigrid driver (mg_fmg.c; mg_solver_internal.h) */
 /* ------------------------------------------------------------------ */
 int mgi_fail(int code, const char *what) { return mgfail(code, what); }
+int mgi_upload(mg_solver *s, const double *h, size_t n, double **d) { return upload(s, h, n, d); }
 double mgi_wall(void) { return wall(); }
 int mgi_start(mg_solver *s) { return start(s); }
 int mgi_smooth(mg_solver *s, int l, int maxit) { return smooth(s, 0, l, maxit, 0); }

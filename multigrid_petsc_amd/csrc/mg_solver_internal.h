@@ -43,6 +43,8 @@ typedef struct mg_level {
     double *ctab, *dtab;    /* -mesh 1/2 (2-D): device tables, 5 coefficients {(i-1), W, C, E, (i+1)} and 1/diag per grid row */
     mg_fset f[2];
     double *p2;             /* Chebyshev: third recurrence vector (fp64) */
+    double *ltab, *gtab, *qtab;   /* y-line Jacobi (pc_type MG_PC_LINE_Y): device tables of the factorised y-tridiagonal part, n doubles each
+                                   * (multipliers, 1 / pivot, N / pivot); ctab / dtab then exist on the uniform mesh too */
 } mg_level;
 
 struct mg_solver {
@@ -95,8 +97,15 @@ enum { MG_CHEBY_ZERO = 0, MG_CHEBY_PLAIN = 1, MG_CHEBY_PROLONG = 2, MG_CHEBY_NOR
 extern int mg_cheby_pass(mg_solver *s, int l, int kind, double *sumsq) __attribute__((weak));
 extern int mg_cheby_tail(mg_solver *s) __attribute__((weak));      /* the levels ltail .. L-1 of one cycle in one kernel */
 
+/* y-line Jacobi (pc_type MG_PC_LINE_Y): mg_line.c holds the only calls of mgk_line_forward_f64 / mgk_line_backward_f64, reached like mg_cheby.c
+ * through WEAK references: a build without it (the host tests' links of mg_solver.c against the plain stand-in of the kernel ABI) needs no new
+ * symbol, and mg_solver_create refuses the line smoother there */
+extern int mg_line_tables(mg_solver *s, int l, const double *ctab_host) __attribute__((weak));   /* factorise and upload level l's tables */
+extern int mg_line_smooth(mg_solver *s, int l, int maxit) __attribute__((weak));   /* KSPSolve on level l: maxit sweeps in place, no swap */
+
 /* the steps of mg_solver.c, for mg_fmg.c (fp64, one rank) */
 int    mgi_fail(int code, const char *what);            /* records the message for mg_last_error(), returns code */
+int    mgi_upload(mg_solver *s, const double *h, size_t n, double **d);   /* a new device array holding n host doubles */
 double mgi_wall(void);
 int    mgi_start(mg_solver *s);                          /* src/solver.c:1512-1523: ||b||, u0 = 0, rnorm[0], every level flag reset, iter = 0 */
 int    mgi_smooth(mg_solver *s, int l, int maxit);       /* KSPSolve on level l (guess as L[l].f[0].guess_nonzero says), no restriction follows */

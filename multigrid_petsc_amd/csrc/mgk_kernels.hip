@@ -71,6 +71,7 @@ extern "C" int mgk_ctx_create(mgk_ctx **out, int device) {
         HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_finish_sum)));
         int rc = mgk_preload_kernels3();
         if (!rc) rc = mgk_preload_krylov();
+        if (!rc) rc = mgk_preload_line();
         if (rc) return rc;
     }
     *out = c;

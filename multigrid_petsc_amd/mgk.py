@@ -173,6 +173,9 @@ def _sigs(L):
         "mgk_lincomb_f64": (i, [vp, G, i, c_dp, C.POINTER(vp), vp, vp]),
         "mgk_scale_to_f64": (i, [vp, G, d, vp, vp, vp, vp]),
         "mgk_paced_copy": (i, [vp, vp, vp, sz, d, i, vp]),
+        # y-line Jacobi: (ctab, ltab, gtab, b, u or None, z) / (qtab, scale, z, u or None, unew)
+        "mgk_line_forward_f64": (i, [vp, G, vp, vp, vp, vp, vp, vp, vp]),
+        "mgk_line_backward_f64": (i, [vp, G, vp, d, vp, vp, vp, vp]),
     }
     for name, (res, args) in S.items():
         f = getattr(L, name)

@@ -1,0 +1,128 @@
+"""The y-line Jacobi cycle (pc_type="yline") against the point-Jacobi cycle and against V-cycle-preconditioned GMRES over it, one GPU, time
+to rtol 1e-7 at Richardson scale 0.8.  Per case ONE process holds two or three solvers of the same configuration; the samples alternate
+between them (drift of the machine hits all alike), after one warm-up of each (first launches, the graph recording, the basis allocation).
+Reported per case: iterations, every sample of solve_seconds, and whether EVERY yline sample lies below EVERY sample of the others.
+
+    python tools/bench_line.py --case 4097:1:30 [--samples 5] [--only yline|jacobi|gmres] [--out FILE]      (run one case per process)
+    python tools/bench_line.py --kernels 4095,2047,1023 [--depths 8,16,32] [--reps 20] [--out FILE]
+
+A case is npts:mesh[:restart]; with a restart length solve_gmres(restart) on a point-Jacobi solver is the third contender.  --only runs one
+alone (one solve of it under a kernel trace).  --kernels times the two passes of a sweep alone (from a guess, in place) on an n x n level with
+random row tables for every built prefetch depth: the measurement behind the default depth."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+from multigrid_petsc_amd.solver import Solver  # noqa: E402
+
+RTOL = 1e-7
+SCALE = 0.8
+
+
+def run(npts, mesh, restart, samples, only):
+    levels = (npts - 1).bit_length() - 1
+    kinds = [only] if only else ["yline", "jacobi"] + (["gmres"] if restart else [])
+    S = {k: Solver(2, npts, levels, v=(3, 3), scale=SCALE, maxiter=2000, rtol=RTOL, mesh=mesh, pc_type="yline" if k == "yline" else "jacobi")
+         for k in kinds}
+    call = {"yline": lambda s: s.solve(), "jacobi": lambda s: s.solve(), "gmres": lambda s: s.solve_gmres(restart)}
+    secs, its = {k: [] for k in kinds}, {}
+    for k, s in S.items():
+        s.set_rhs_problem()
+        call[k](s)                                                        # warm-up
+    for _ in range(samples):
+        for k, s in S.items():
+            s.reset()
+            its[k] = call[k](s)
+            secs[k].append(s.solve_seconds)
+    row = {"npts": npts, "levels": levels, "mesh": mesh, "scale": SCALE, "restart": restart, "rtol": RTOL, "samples": samples}
+    for k, s in S.items():
+        rn = s.rnorm
+        row[k] = {"iterations": its[k], "converged": bool(rn[-1] <= RTOL * s.bnorm), "relative_residual": float(rn[-1] / rn[0]),
+                  "seconds": secs[k], "seconds_median": statistics.median(secs[k])}
+        s.close()
+    for k in kinds:
+        if k != "yline" and "yline" in kinds:
+            row[k + "_over_yline"] = row[k]["seconds_median"] / row["yline"]["seconds_median"]
+            row["every_yline_sample_below_every_%s_sample" % k] = max(secs["yline"]) < min(secs[k])
+    return row
+
+
+def kernels(sizes, depths, reps):
+    """microseconds of one forward and one backward pass (from a guess, in place) per size and prefetch depth, median of `reps`"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import line_reference as LR
+    from row_tables import _rt_tables
+    from multigrid_petsc_amd.mgk import Mgk
+    m = Mgk(0)
+    L = m.L
+    rows = []
+    for n in sizes:
+        ct = _rt_tables(np.random.default_rng(n + 1), n)[0]           # (the time of a pass does not depend on the values)
+        l, g, q = LR.tables(ct)
+        geo = m.geom(2, n)
+        rng = np.random.default_rng(n)
+        b, u = m.to_field(geo, rng.uniform(-1, 1, n * n)), m.to_field(geo, rng.uniform(-1, 1, n * n))
+        z = m.field(geo)
+        t = [m.upload(x) for x in (ct, l, g, q)]
+        G = C.byref(geo)
+        row = {"n": n, "reps": reps}
+        for d in depths:
+            L.mgk_set_tuning(-1, d)
+            us = {"forward": [], "backward": []}
+            for r in range(reps + 2):
+                m.sync()
+                t0 = time.perf_counter()
+                m._chk(L.mgk_line_forward_f64(m.ctx, G, t[0], t[1], t[2], b, u, z, None))
+                m.sync()
+                t1 = time.perf_counter()
+                m._chk(L.mgk_line_backward_f64(m.ctx, G, t[3], 1e-3, z, u, u, None))
+                m.sync()
+                t2 = time.perf_counter()
+                if r >= 2:
+                    us["forward"].append(1e6 * (t1 - t0))
+                    us["backward"].append(1e6 * (t2 - t1))
+            row["depth_%d" % d] = {k: {"median_us": statistics.median(v), "min_us": min(v)} for k, v in us.items()}
+        L.mgk_set_tuning(-1, -1)
+        for p in [b, u, z] + t:
+            m.free(p)
+        rows.append(row)
+    m.close()
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", default=None, help="npts:mesh[:restart]")
+    ap.add_argument("--samples", type=int, default=5)
+    ap.add_argument("--only", default=None, choices=["yline", "jacobi", "gmres"])
+    ap.add_argument("--kernels", default=None, help="level sizes n (n + 1 a power of two), comma separated")
+    ap.add_argument("--depths", default="8,16,32")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.kernels:
+        rows = kernels([int(x) for x in a.kernels.split(",")], [int(x) for x in a.depths.split(",")], a.reps)
+    elif a.case:
+        f = a.case.split(":")
+        rows = [run(int(f[0]), int(f[1]), int(f[2]) if len(f) > 2 else 0, a.samples, a.only)]
+    else:
+        ap.error("give --case or --kernels")
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    if a.out:
+        with open(a.out, "a") as fo:
+            for r in rows:
+                fo.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
