@@ -11,17 +11,18 @@
  * the reference file:line it follows (paths relative to /root/reference).
  *
  * PARITY PINNING STATUS
- *  - integer half (index maps, ranges): pinned against the reference outputs
- *    recorded in SURVEY.md section 8(c2) (tests/golden/survey_c2.json).
- *  - floating-point half: the arithmetic lives in PETSc (third party, version
- *    unpinned, not installed, not vendored) and the reference ships no tests
- *    or golden vectors => "parity unpinned" by the reference.  It is pinned
- *    instead by (i) the closed-form discrete-eigenvector known answer,
- *    (ii) bit-equality of two independent restatements in this file
- *    (assembled-CSR path that follows solver.c's MatSetValue loops, and a
- *    matrix-free stencil path), (iii) committed vectors from a scipy.sparse
- *    restatement (tests/golden/make_golden.py -> vcycle_golden.npz), see
- *    tests/test_oracle.py.
+ *  - everything the reference computes on the HOST before a solve is pinned by RECORDED REFERENCE OUTPUT: oracle/ref_record.c runs the
+ *    reference's unmodified matbuild.c / mesh.c / problem.c / solver.c (SetUpMesh .. Assemble) under our own main and records the index maps,
+ *    ranges, grid ids, sizes, h, transfer stencils, coordinates and every MatSetValue / VecSetValue call; tests/golden/ref_maps.npz and
+ *    ref_assembly.npz hold those numbers, and tests/test_reference_fixtures_cpu.py requires, bit for bit: the integer half (mgo_mapping_2d,
+ *    mgo_get_ranges, mgo_grid_ids, mgo_grid_n, mgo_level_total_2d for -map 0/1/2, 1..8 ranks, -grids >= -levels), the assembled values
+ *    (mgo_build_A / _A_mesh / _R / _P with their sparsity pattern, mgo_rhs(_mesh), mgo_coords_*, mgo_mesh_h, h, the 3x3 stencils) on meshes
+ *    0/1/2, and mgo_error_norms(_mesh) against GetError on a fixed field.  tests/golden/survey_c2.json (two hand-copied cases) stays.
+ *  - what stays UNPINNED by the reference is exactly the PETSc semantics listed below (MatMult's order, Richardson, Jacobi, the residual,
+ *    the norm): PETSc is third party, version unpinned, not installed, not vendored, and the reference ships no vectors of a solve.  They
+ *    are pinned instead by (i) the closed-form discrete-eigenvector known answer, (ii) bit-equality of two independent restatements in this
+ *    file (assembled-CSR path that follows solver.c's MatSetValue loops, and a matrix-free stencil path), (iii) committed vectors from a
+ *    scipy.sparse restatement (tests/golden/make_golden.py -> vcycle_golden.npz), see tests/test_oracle.py.
  *  - 3-D has no reference implementation at all (DIMENSION is 2,
  *    include/mesh.h:17); the 3-D branches extend the 2-D semantics by analogy
  *    and are marked "3-D extension".

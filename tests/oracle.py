@@ -66,6 +66,7 @@ class Oracle:
         L.mgo_rhs_mesh.argtypes = [C.c_int, C.c_int, C.c_void_p]
         L.mgo_error_norms.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.mgo_coords_uniform.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.mgo_coords_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.mgo_get_ranges.argtypes = [C.c_int, C.c_int, C.c_void_p]
         L.mgo_mapping_2d.restype = C.c_int
         L.mgo_mapping_2d.argtypes = [C.c_int] * 6 + [C.c_void_p] * 3

@@ -962,6 +962,75 @@ def nonsymmetric_operators_keep_petsc_semantics(L, orc):
         L.MatDestroy(C.byref(mR)); L.MatDestroy(C.byref(mP))
 
 
+def reference_streams(L, fixtures):
+    """The drop-in fed with the reference's OWN call stream (tests/golden/ref_assembly.npz through ref_fixtures.load_assembly): every recorded
+    MatSetValue / VecSetValue replayed into MatCreateAIJ / MatSetValue / MatAssemblyBegin/End and VecSetValue in the recorded order -- R and P
+    and the levels of several grids do not come with ascending columns, as _assemble's matrices do.
+    One grid per level (-grids == -levels): MatView must name a recognised device operator for A (5-point stencil; with row-dependent
+    coefficients on -mesh 1/2), R (full weighting) and P (bilinear prolongation), and MatMult on a uniform(-1, 1) vector must equal the
+    canonical product (oracle/mgo.h: columns ascending, separate multiply and add, the sum starts at 0.0) BIT FOR BIT.
+    Levels of several grids (-grids > -levels): 1e-11 * max(1, max|want|), this file's tolerance for operators run as several kernels
+    (nonsymmetric_operators_keep_petsc_semantics).  b[0]: VecGetArray returns the recorded values exactly, at npts 65 / 129 too.
+    Returns the number of comparisons made."""
+    import ref_fixtures as RF
+    L.PetscInitialize(None, None, None, None)
+    L.VecCreateSeq.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    rng = np.random.default_rng(41)
+    names = {RF.KIND_A: {0: "matrix-free 5-point stencil\n", 1: "matrix-free 5-point stencil with row-dependent coefficients\n",
+                         2: "matrix-free 5-point stencil with row-dependent coefficients\n"},
+             RF.KIND_R: dict.fromkeys((0, 1, 2), "matrix-free full weighting\n"), RF.KIND_P: dict.fromkeys((0, 1, 2), "matrix-free bilinear prolongation\n")}
+    done = 0
+    for case, c in fixtures.items():
+        mesh, npts, grids, levels, _, full = case
+        want_b = RF.stream_vector(c)
+        n0 = want_b.size
+        b = C.c_void_p()
+        L.VecCreateSeq(1, n0, C.byref(b))
+        row, _, val, _ = RF.stream_select(c, RF.KIND_B, 0)
+        for r, v in zip(row.tolist(), val.tolist()):
+            L.VecSetValue(b, r, v, INSERT)
+        L.VecAssemblyBegin(b); L.VecAssemblyEnd(b)
+        assert RF.same_bits(_get(L, b, n0), want_b), (case, "b[0] through VecSetValue / VecGetArray")
+        done += 1
+        L.VecDestroy(C.byref(b))
+        if not full:
+            continue
+        totals = [int(c["row"][c["obj"] == 32 * RF.KIND_A + l].max()) + 1 for l in range(levels)]
+        objs = [int(o) for o in dict.fromkeys(c["obj"].tolist()) if o // 32 != RF.KIND_B]
+        for o in objs:
+            kind, l = o // 32, o % 32
+            sel = np.nonzero(c["obj"] == o)[0]
+            assert np.array_equal(sel, np.arange(sel[0], sel[0] + sel.size)), (case, o, "the calls of one matrix are contiguous")
+            nr, nc = RF.stream_shape(c, kind, l, totals)
+            m = C.c_void_p()
+            L.MatCreateAIJ(1, nr, nc, -1, -1, 30, None, 0, None, C.byref(m))
+            for r, cc, v, md in zip(c["row"][sel].tolist(), c["col"][sel].tolist(), c["val"][sel].tolist(), c["mode"][sel].tolist()):
+                L.MatSetValue(m, r, cc, v, md)
+            L.MatAssemblyBegin(m, FINAL); L.MatAssemblyEnd(m, FINAL)
+            x, y = C.c_void_p(), C.c_void_p()
+            L.MatCreateVecs(m, C.byref(x), C.byref(y))
+            xv = rng.uniform(-1, 1, nc)
+            _set(L, x, xv)
+            L.MatMult(m, x, y)
+            got = _get(L, y, nr)
+            want = RF.csr_mult_canonical(*RF.stream_csr(c, kind, l, nr), xv)
+            tag = (case, "A res pro".split()[kind], l)
+            if grids == levels:
+                view = _device_operator(L, m)
+                assert view.endswith(names[kind][mesh]) and "assembled AIJ" not in view, (tag, view)
+                if not RF.same_bits(got, want):
+                    q = int(np.nonzero(got != want)[0][0])
+                    raise AssertionError((tag, "MatMult differs from the canonical product: first at row", q, float(got[q]).hex(), float(want[q]).hex()))
+                done += 2
+            else:
+                err = float(np.max(np.abs(got - want)))
+                assert err <= 1e-11 * max(1.0, float(np.abs(want).max())), (tag, err)
+                done += 1
+            L.VecDestroy(C.byref(x)); L.VecDestroy(C.byref(y))
+            L.MatDestroy(C.byref(m))
+    return done
+
+
 if __name__ == "__main__":      # python tests/shim_semantics.py <shared library> <function name>: one check in a process of its own
     import os
     import sys
@@ -971,6 +1040,7 @@ if __name__ == "__main__":      # python tests/shim_semantics.py <shared library
     {"lazy": lazy_temporaries_keep_petsc_semantics, "spec": speculative_sweep_is_adopted_only_when_nothing_changed,
      "keepr": residual_left_deferred_by_the_norm_pass, "tailrec": recorded_coarse_subcycle_keeps_petsc_semantics, "pcmgtail": pcmg_level_vectors_after_the_tail_launch, "lu": richardson_with_lu_is_damped_not_exact,
      "nonsym": nonsymmetric_operators_keep_petsc_semantics,
+     "refstreams": lambda L_, o_: print("reference_streams:", reference_streams(L_, __import__("ref_fixtures").load_assembly()), "comparisons"),
      "random": lambda L_, o_: random_programs_keep_petsc_semantics(L_, o_, seed=int(sys.argv[3]) if len(sys.argv) > 3 else 1,
                                                                    nprog=int(sys.argv[4]) if len(sys.argv) > 4 else 40)}[sys.argv[2]](lib, Oracle())
     print("SEMANTICS_OK", sys.argv[2])

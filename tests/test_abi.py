@@ -106,12 +106,15 @@ def test_slab_split_is_nested_and_covers(npts, ldist, nranks):
 def test_implicit_maps_equal_the_reference_maps_bit_exactly(npts, levels, style):
     """a9: the product keeps no index arrays; its formula maps must reproduce, entry for entry, the grid->global and
     global->(i,j,g) arrays the reference builds (src/matbuild.c:146-323, restated in the oracle) for every -map style
-    when each level holds one grid, and its ranges for any number of ranks."""
+    when each level holds one grid, and its ranges for any number of ranks.  The same against the arrays the reference itself computed
+    (tests/golden/ref_maps.npz, recorded by oracle/ref_record.c): the oracle is a restatement, the recording is not."""
     import ctypes as C
+    import ref_fixtures as RF
     from multigrid_petsc_amd import solver as S
     from oracle import Oracle
     orc = Oracle()
     L = S._lib()
+    recorded = RF.load_maps()[0]
     for l in range(levels):
         n = L.mg_grid_n(npts, l)
         tot = n * n
@@ -127,6 +130,31 @@ def test_implicit_maps_equal_the_reference_maps_bit_exactly(npts, levels, style)
                 L.mg_global_to_grid(2, n, idx, C.byref(k), C.byref(i), C.byref(j))
                 assert (i.value, j.value, l) == tuple(glob[3 * idx:3 * idx + 3])
             assert np.array_equal(S.get_ranges(tot, procs), ranges)
+        for procs in (1, 2, 3, 4, 8):
+            rec = recorded[(npts, levels, levels, style, procs)]
+            assert int(rec["grids"][l]) == 1 and int(rec["total"][l]) == tot and rec["grid"][l][0].shape == (n, n)     # mg_grid_n
+            mine = np.array([L.mg_grid_to_global(2, n, 0, i, j) for i in range(n) for j in range(n)], dtype=np.int32)
+            assert RF.same_bits(mine, rec["grid"][l][0].reshape(-1))
+            back = np.zeros((tot, 3), dtype=np.int32)
+            k, i, j = C.c_int(), C.c_int(), C.c_int()
+            for idx in range(tot):
+                L.mg_global_to_grid(2, n, idx, C.byref(k), C.byref(i), C.byref(j))
+                back[idx] = (i.value, j.value, l)
+            assert RF.same_bits(back, rec["glob"][l])
+            assert RF.same_bits(np.asarray(S.get_ranges(tot, procs), dtype=np.int32), rec["ranges"][l])
+
+
+def test_teeth_of_the_recorded_map_comparison():
+    """the helper the comparison above uses reports two swapped map entries and a ranges entry off by one"""
+    import ref_fixtures as RF
+    rec = RF.load_maps()[0][(17, 3, 3, 1, 3)]
+    grid, ranges = rec["grid"][0][0].reshape(-1), rec["ranges"][0]
+    assert RF.same_bits(grid.copy(), grid) and RF.same_bits(ranges.copy(), ranges)
+    swapped = grid.copy()
+    swapped[[17, 18]] = swapped[[18, 17]]
+    off = ranges.copy()
+    off[1] += 1
+    assert not RF.same_bits(swapped, grid) and not RF.same_bits(off, ranges)
 
 
 def _petsc_surface():

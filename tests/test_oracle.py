@@ -226,7 +226,14 @@ def test_oracle_operators_match_committed_vectors(orc, dim, nf):
 @pytest.mark.parametrize("npts,levels", [(9, 3), (17, 4), (33, 5)])
 @pytest.mark.parametrize("procs", [1, 2, 4, 8])
 def test_ranges_match_committed_vectors(orc, npts, levels, procs):
+    """the committed ranges come from a Python formula (tests/golden/make_golden.py: maps); the reference's own, recorded by
+    oracle/ref_record.c (tests/golden/ref_maps.npz), must be the same numbers"""
+    import ref_fixtures as RF
     want = NPZ["ranges_n%d_p%d" % (npts, procs)]
+    full, ranges_only = RF.load_maps()
+    case = (npts, levels, levels, 2, procs)
+    recorded = ranges_only[case] if case in ranges_only else full[case]["ranges"]
+    assert RF.same_bits(np.asarray(want, dtype=np.int32), recorded)
     for l in range(levels):
         for style in (0, 1, 2):
             _, _, ranges = _maps(orc, npts, levels, levels, style, procs, l)

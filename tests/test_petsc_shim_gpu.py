@@ -640,6 +640,19 @@ def test_nonsymmetric_operators_keep_petsc_semantics():
     assert p.returncode == 0 and "SEMANTICS_OK nonsym" in p.stdout, (p.returncode, p.stdout[-3000:])
 
 
+def test_reference_streams_replayed_into_the_drop_in():
+    """the reference's own recorded MatSetValue / VecSetValue calls (tests/golden/ref_assembly.npz) in their own order on the real
+    libmgpetsc.so: A, R and P of the one-grid-per-level cases are recognised and their MatMult equals the canonical product of oracle/mgo.h
+    bit for bit, the levels of several grids within 1e-11, b[0] exact (a process of its own: it reads MatView's line from the process's
+    stdout; see tests/shim_semantics.py: reference_streams)"""
+    import subprocess
+    import sys
+    lib = os.path.join(ROOT, "multigrid_petsc_amd", "libmgpetsc.so")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "shim_semantics.py"), lib, "refstreams"], stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert p.returncode == 0 and "SEMANTICS_OK refstreams" in p.stdout, (p.returncode, p.stdout[-3000:])
+
+
 def test_random_programs_of_petsc_calls_keep_petsc_semantics():
     """programs of PETSc calls drawn at random over a two-level set-up against a call-by-call numpy model -- the fragments of the reference's loop
     started and interrupted wherever the draw says (a process of its own; see tests/shim_semantics.py: random_programs_keep_petsc_semantics)"""

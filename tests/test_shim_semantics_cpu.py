@@ -70,6 +70,12 @@ def test_nonsymmetric_operators_keep_petsc_semantics_on_the_mock(mock_shim):
     _check(mock_shim, "nonsym")
 
 
+def test_reference_streams_replayed_into_the_drop_in_on_the_mock(mock_shim):
+    """the reference's own recorded MatSetValue / VecSetValue calls (tests/golden/ref_assembly.npz) in their own order: recognised operators,
+    MatMult equal to the canonical product bit for bit, b[0] exact; see tests/shim_semantics.py: reference_streams"""
+    _check(mock_shim, "refstreams")
+
+
 def test_random_programs_of_petsc_calls_keep_petsc_semantics_on_the_mock(mock_shim):
     """random_programs_keep_petsc_semantics: 25 programs of up to 60 calls (seed 1); round 3 ran 7 seeds x 40 programs over the mock: no deviation"""
     _check(mock_shim, "random", "1", "25")
