@@ -22,6 +22,61 @@ typedef enum { MG_KSP_RICHARDSON = 0, MG_KSP_CHEBYSHEV = 1 } mg_ksp_type;
 typedef enum { MG_PREC_FP64 = 0, MG_PREC_MIXED = 1 } mg_precision;
 typedef enum { MG_PC_JACOBI = 0, MG_PC_LINE_Y = 1 } mg_pc_type;
 
+/* the bits of mg_config.fuse: one fused pass (or family of passes) each.  The VALUES are ABI: tests, bench.py, the tools and
+ * `mgpoisson -mg_fuse N` pass numerals.  "(bit N)" is the name the bit goes by in DESIGN.md, the tests and the profiles. */
+typedef enum mg_fuse_bits {
+    /* (bit 0) final residual fused with its norm (no rv write) */
+    MG_FUSE_RESNORM = 1,
+    /* (bit 1) prolongation fused into the first post-smoothing sweep */
+    MG_FUSE_PROLONG_SWEEP = 2,
+    /* (bit 2) pre-restriction residual fused with the restriction */
+    MG_FUSE_RES_RESTRICT = 4,
+    /* (bit 3) the residual norm that closes a cycle is evaluated by the kernel that also makes the first pre-smoothing sweep of the
+     * next cycle (adopted only if a next cycle runs) */
+    MG_FUSE_NORM_SWEEP = 8,
+    /* (bit 4; mixed precision) the fp64 correction u += e and the fp64 residual -> fp32 in one pass */
+    MG_FUSE_MIXED_CORRECT = 16,
+    /* (bit 5) pairs of sweeps in one pass (temporal blocking, levels >= pair_min_n, both precisions) */
+    MG_FUSE_PAIRS = 32,
+    /* (bit 6, value 64) unassigned: callers pass it (fuse = 127, 63 | 64), so it stays accepted and is ignored */
+    /* (bit 7; testing) bit 2 also below 255^3, where two short kernels are quicker */
+    MG_FUSE_RES_RESTRICT_SMALL = 128,
+    /* (bit 8) the fused residual+restriction also writes the coarse level's first (zero-guess) sweep */
+    MG_FUSE_COARSE_ZERO_SWEEP = 256,
+    /* (bit 9) the levels that fit in LDS (n <= 15 in 3-D, <= 63 in 2-D) run as ONE kernel per cycle (mgk_tail_cycle_*) */
+    MG_FUSE_LDS_TAIL = 512,
+    /* (bit 10; fp64, 3-D, full-row shapes n = 127 .. 1023, whole grids and z-slabs) the pass of bit 3 makes the first TWO sweeps of the
+     * next cycle (mgk_jacobi2_sumsq_f64 / _slab_f64) and the last pre-smoothing sweep runs inside the restriction's pass
+     * (mgk_sweep_residual_restrict_f64 / _slab_f64): the fine level moves 99 instead of 115 B per unknown and cycle */
+    MG_FUSE_SWEEP_RESTRICT = 1024,
+    /* (bit 11; 3-D whole levels that sweep in pairs: fp32 up to 1023^3, fp64 up to 511^3) a pre-smoothing of >= 3 sweeps from the zero
+     * guess starts with ONE pass that makes three of them and reads b alone (mgk_jacobi2_zero_*) */
+    MG_FUSE_ZERO_TRIPLE = 2048,
+    /* (bit 12; fp64, 3-D, level 0 of 511- / 1023-wide whole grids, v0 = 3) post-smoothing is ONE pass for the prolongation and two
+     * sweeps (mgk_prolong_jacobi2_f64); the third sweep is the first stage of the two-sweep pass that evaluates the norm
+     * (mgk_jacobi2_sumsq_mid_f64): 91 B per fine unknown and cycle.  The iterate the norm belongs to is not stored; when the
+     * iteration stops one more sweep materialises it */
+    MG_FUSE_PROLONG_PAIR = 4096,
+    /* (bit 13; 2-D, fp64, Richardson, uniform and stretched meshes) THREE sweeps per pass (mgk_jacobi3_2d_*): pre-smoothing from the
+     * zero guess in one pass over b, post-smoothing in one pass with the prolongation, and the norm pass of bit 3 makes all three
+     * pre-smoothing sweeps of the next cycle: three passes over a level per V(3,3) cycle */
+    MG_FUSE_TRIPLE_2D = 8192,
+    /* (bit 14; round 3; nranks > 1) bit 12's three passes on z-slabs -- mgk_prolong_jacobi2_slab_f64 (the neighbours' boundary and
+     * second planes of u and of the coarse u arrive in two grouped exchanges hidden behind the interior planes),
+     * mgk_jacobi2_sumsq_mid_slab_f64, the plain fused residual + restriction: every rank moves 91 instead of 99 B per fine unknown
+     * and cycle */
+    MG_FUSE_PROLONG_PAIR_SLAB = 16384,
+    /* (bit 15, 32768; KSPCHEBYSHEV, fp64, one rank) the smoothings with exactly three steps of 2-D levels run as ONE three-step pass
+     * each (mgk_cheby3_2d_*: the passes, swaps and bytes of bit 13's Richardson cycle, coarse-level graph included), and the levels
+     * that fit in LDS as one kernel per cycle in 2-D and 3-D with any step counts (mgk_tail_cycle_cheby_f64, with bit 9); off: every
+     * step is a launch of its own */
+    MG_FUSE_CHEBY = 32768,
+    /* what mg_config.fuse = -1 selects: bits 0-5 and 8-15 */
+    MG_FUSE_DEFAULT = MG_FUSE_RESNORM | MG_FUSE_PROLONG_SWEEP | MG_FUSE_RES_RESTRICT | MG_FUSE_NORM_SWEEP | MG_FUSE_MIXED_CORRECT | MG_FUSE_PAIRS |
+                      MG_FUSE_COARSE_ZERO_SWEEP | MG_FUSE_LDS_TAIL | MG_FUSE_SWEEP_RESTRICT | MG_FUSE_ZERO_TRIPLE | MG_FUSE_PROLONG_PAIR |
+                      MG_FUSE_TRIPLE_2D | MG_FUSE_PROLONG_PAIR_SLAB | MG_FUSE_CHEBY
+} mg_fuse_bits;
+
 /* options of the reference driver (src/poisson.c:51-59, poisson.in) + the PETSc options that
  * KSPSetFromOptions (src/solver.c:1476,1492,1509) would pick up for the smoother */
 typedef struct mg_config {
@@ -39,37 +94,9 @@ typedef struct mg_config {
     int rank, nranks;   /* z-slab decomposition over `nranks` GPUs (1: whole grid) */
     int dist_min_n;     /* levels with n >= dist_min_n stay distributed, coarser ones are replicated; <=0: default 255
                          * (below that a slab sweep is shorter than the latency of its halo exchange) */
-    int fuse;           /* bit 0: final residual fused with its norm (no rv write); bit 1: prolongation fused into the
-                         * first post-smoothing sweep; bit 2: pre-restriction residual fused with the restriction;
-                         * bit 3: the residual norm that closes a cycle is evaluated by the kernel that also makes the first
-                         * pre-smoothing sweep of the next cycle (adopted only if a next cycle runs); bit 4 (mixed precision): the
-                         * fp64 correction u += e and the fp64 residual -> fp32 in one pass; bit 5: pairs of sweeps in one pass
-                         * (temporal blocking, levels >= pair_min_n, both precisions); bit 7 (testing): bit 2 also below 255^3, where two short
-                         * kernels are quicker; bit 8: the fused residual+restriction also writes the coarse level's first (zero-guess)
-                         * sweep; bit 9: the levels that fit in LDS (n <= 15 in 3-D, <= 63 in 2-D) run as ONE kernel per cycle (mgk_tail_cycle_*);
-                         * bit 10 (fp64, 3-D, full-row shapes n = 127 .. 1023, whole grids and z-slabs): the pass of bit 3 makes the first TWO
-                         * sweeps of the next cycle (mgk_jacobi2_sumsq_f64 / _slab_f64) and the last pre-smoothing sweep runs inside the
-                         * restriction's pass (mgk_sweep_residual_restrict_f64 / _slab_f64): the fine level moves 99 instead of 115 B per
-                         * unknown and cycle;
-                         * bit 11 (3-D whole levels that sweep in pairs: fp32 up to 1023^3, fp64 up to 511^3): a pre-smoothing of >= 3 sweeps
-                         * from the zero guess starts with ONE pass that makes three of them and reads b alone (mgk_jacobi2_zero_*);
-                         * bit 12 (fp64, 3-D, level 0 of 511- / 1023-wide whole grids, v0 = 3): post-smoothing is ONE pass for the prolongation and two
-                         * sweeps (mgk_prolong_jacobi2_f64); the third sweep is the first stage of the two-sweep pass that evaluates the
-                         * norm (mgk_jacobi2_sumsq_mid_f64): 91 B per fine unknown and cycle.  The iterate the norm belongs to is not
-                         * stored; when the iteration stops one more sweep materialises it;
-                         * bit 13 (2-D, fp64, Richardson, uniform and stretched meshes): THREE sweeps per pass (mgk_jacobi3_2d_*): pre-smoothing
-                         * from the zero guess in one pass over b, post-smoothing in one pass with the prolongation, and the norm pass of
-                         * bit 3 makes all three pre-smoothing sweeps of the next cycle: three passes over a level per V(3,3) cycle;
-                         * bit 14 (round 3; nranks > 1): bit 12's three passes on z-slabs -- mgk_prolong_jacobi2_slab_f64 (the neighbours' boundary and
-                         * second planes of u and of the coarse u arrive in two grouped exchanges hidden behind the interior planes),
-                         * mgk_jacobi2_sumsq_mid_slab_f64, the plain fused residual + restriction: every rank moves 91 instead of 99 B per fine
-                         * unknown and cycle;
-                         * bit 15 (32768; KSPCHEBYSHEV, fp64, one rank): the smoothings with exactly three steps of 2-D levels run as ONE three-step
-                         * pass each (mgk_cheby3_2d_*: the passes, swaps and bytes of bit 13's Richardson cycle, coarse-level graph included), and the
-                         * levels that fit in LDS as one kernel per cycle in 2-D and 3-D with any step counts (mgk_tail_cycle_cheby_f64, with bit 9);
-                         * off: every step is a launch of its own.  Like the other bits it exists so that tests can run the unfused path as the
-                         * reference; which path runs is otherwise decided by what the solver sees (dimension, v0, ranks);
-                         * default (-1): bits 0-5 and 8-15 on */
+    int fuse;           /* which fused passes a cycle may use: a mask of mg_fuse_bits (above).  Every bit exists so that tests can run the
+                         * unfused path as the reference; which path runs is otherwise decided by what the solver sees (dimension, v0,
+                         * ranks).  -1 selects the default set, MG_FUSE_DEFAULT */
     int overlap;        /* nranks > 1: halo of sweep k on the comm stream while sweep k's interior runs; default on (-1) */
     int graph;          /* replay the launch-bound coarse levels as one captured HIP graph; default on (-1) */
     int pair_min_n;     /* levels with n >= pair_min_n run their sweeps two per pass (fuse bit 5); <=0: default 255 (3-D), 2047 (2-D) */

@@ -37,7 +37,7 @@ static int fmg_check(const mg_solver *s, int nu) {
 static int interpolate(mg_solver *s, int l) {
     mg_level *Lf = &s->L[l];
     mg_fset *F = &Lf->f[0], *C = &s->L[l + 1].f[0];
-    const int v0 = s->cfg.v[0], fused = (s->cfg.fuse & 2) != 0;
+    const int v0 = s->cfg.v[0], fused = (s->cfg.fuse & MG_FUSE_PROLONG_SWEEP) != 0;
     F->guess_nonzero = 1;
     F->pre_done = 0; F->jz_ready = 0; F->last_sweep_pending = 0;
     if (fused && s->cfg.dim == 3 && v0 >= 2 && mgk_interp_jacobi2_ok_f64(&F->g, &C->g)) {
@@ -52,7 +52,7 @@ static int interpolate(mg_solver *s, int l) {
         CHK(mgk_memset0(s->ctx, F->u, sizeof(double) * (size_t)F->g.total, NULL));
         CHK(mgk_prolong_add_f64(s->ctx, &F->g, &C->g, (const double *)C->u, (double *)F->u, NULL));
     }
-    F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+    mgi_u_rewritten(F);
     return 0;
 }
 
@@ -68,7 +68,7 @@ static int tail_fmg(mg_solver *s, int nu) {
     }
     mg_fset *F = &s->L[lt].f[0];
     CHK(mgk_tail_fmg_f64(s->ctx, &F->g, nl, n, k7, di, s->cfg.scale, s->cfg.v[0], s->cfg.v[1], nu, (const double *)F->b, (double *)F->u, NULL));
-    F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+    mgi_u_rewritten(F);
     return 0;
 }
 

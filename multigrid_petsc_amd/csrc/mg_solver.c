@@ -94,6 +94,9 @@ static const mg_ops OPS[2] = {
     {8, jr_64, jz_64, rs_64, rf_64, pa_64, pj_64, rr_64, rg_64, fin_64, rrz_64, j2_64, j2s_64, pjr_64, rrr_64, rrs_64, tc_64},
     {4, jr_32, jz_32, rs_32, rf_32, pa_32, pj_32, rr_32, rg_32, fin_32, rrz_32, j2_32, j2s_32, pjr_32, rrr_32, rrs_32, tc_32},
 };
+/* the coefficient arguments of the mgk_*jacobi3_2d* kernels for level L_ (coef, dinv, scale, ctab, dtab): the level's constants on the uniform
+ * mesh, its row tables under -mesh 1/2.  Reads `s` and the flag `mesh` of the calling function */
+#define J3_COEFS(L_) mesh ? NULL : (L_)->coef, mesh ? 1.0 : (L_)->dinv, s->cfg.scale, mesh ? (L_)->ctab : NULL, mesh ? (L_)->dtab : NULL
 
 /* ------------------------------------------------------------------ */
 /* integer half                                                        */
@@ -264,10 +267,14 @@ static int upload(mg_solver *s, const double *h, size_t n, double **d);
 static int cheby_fused(const mg_solver *s);
 static int cheby_steps_by_launch(const mg_solver *s, int l);
 
+/* KSPSolve's max_it on level l: v1 on the coarsest level, v0 above it (src/solver.c:1531,1536); level 0 takes v0 even when it is the only level
+ * (`l > 0`: cheby_steps_by_launch asks for level 0; descend and descend_restrict read level l - 1, so they run for l >= 1 alone) */
+static inline int level_sweeps(const mg_solver *s, int l) { return (l > 0 && l == s->levels - 1) ? s->cfg.v[1] : s->cfg.v[0]; }
+
 /* distributed level: the (nx, ny, 2) field through which the neighbours' second planes of u travel (two-sweep passes) */
 static int alloc_far(mg_solver *s, mg_level *L, int P) {
     mg_fset *F = &L->f[P];
-    if (!L->distributed || !(s->cfg.fuse & 32) || s->cfg.dim != 3) return 0;
+    if (!L->distributed || !(s->cfg.fuse & MG_FUSE_PAIRS) || s->cfg.dim != 3) return 0;
     int rc = (P == 0) ? mgk_geom_init(&F->gfar, 3, L->n, L->n, 2) : mgk_geom_init_f32(&F->gfar, 3, L->n, L->n, 2);
     if (rc) return rc;
     void *q = NULL;
@@ -275,7 +282,7 @@ static int alloc_far(mg_solver *s, mg_level *L, int P) {
     CHK(mgk_malloc(s->ctx, &q, bytes));
     CHK(mgk_memset0(s->ctx, q, bytes, NULL));
     F->far = q;
-    if (P == 0 && (s->cfg.fuse & 1024)) {
+    if (P == 0 && (s->cfg.fuse & MG_FUSE_SWEEP_RESTRICT)) {
         void *q2 = NULL, *q3 = NULL;
         CHK(mgk_malloc(s->ctx, &q2, bytes));
         F->far2 = q2;
@@ -324,13 +331,13 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         const int n0 = mg_grid_n(cfg->npts, 0);
         s->cfg.dist_min_n = n0 < 255 ? n0 : 255;
     }
-    if (s->cfg.fuse < 0) s->cfg.fuse = 63 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768;
+    if (s->cfg.fuse < 0) s->cfg.fuse = MG_FUSE_DEFAULT;
     if (s->cfg.pair_min_n <= 0) s->cfg.pair_min_n = (cfg->dim == 3) ? 255 : 2047;   /* where a two-sweep pass beats two sweeps
                                                                                       * (255^3: 0.107 ms against 2 x 0.063) */
     /* y-line Jacobi: the passes that bake point Jacobi in are off (bits 1, 3, 5, 8-15); the fused residual + norm (0) and residual +
      * restriction (2) stay, the coarse levels run by launch inside the HIP graph */
-    if (s->cfg.pc_type == MG_PC_LINE_Y) s->cfg.fuse &= ~(2 | 8 | 32 | 0xff00);
-    if (s->cfg.mesh) s->cfg.fuse &= ~(16 | 128);   /* row-dependent coefficients (2-D, fp64): the same fused cycle on the row-table forms of the kernels */
+    if (s->cfg.pc_type == MG_PC_LINE_Y) s->cfg.fuse &= ~MG_FUSE_POINT_JACOBI_PASSES;
+    if (s->cfg.mesh) s->cfg.fuse &= ~MG_FUSE_NO_ROW_TABLE_FORM;   /* row-dependent coefficients (2-D, fp64): the same fused cycle on the row-table forms of the kernels */
     if (s->cfg.overlap < 0) s->cfg.overlap = 1;
     if (s->cfg.graph < 0) s->cfg.graph = 1;
     if (s->cfg.nranks < 1) s->cfg.nranks = 1;
@@ -403,7 +410,7 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         if (mixed) {
             /* fp64 only where the outer defect correction lives (level 0: u, b); fp32 on every level */
             if (l == 0 && (rc = alloc_fset(s, &L->f[0], 8, 0))) { mg_solver_destroy(s); return rc; }
-            if (l == 0 && (s->cfg.fuse & 16) && !L->distributed) {          /* spare fp64 field of the fused correction + residual pass */
+            if (l == 0 && (s->cfg.fuse & MG_FUSE_MIXED_CORRECT) && !L->distributed) {          /* spare fp64 field of the fused correction + residual pass */
                 void *q = NULL;
                 if ((rc = mgk_malloc(s->ctx, &q, sizeof(double) * (size_t)L->f[0].g.total))) { mg_solver_destroy(s); return mgfail(rc, "mg_solver_create: field"); }
                 L->f[0].tmp = q;
@@ -423,7 +430,7 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
      * and everything below it fit in LDS (n <= mgk_tail_max_n) -- and at least two levels are left, else a tail is no gain */
     s->ltail = 0;
     const int cheby_tail = cheby_fused(s) && s->cfg.v[0] >= 0 && s->cfg.v[1] >= 0 && s->cfg.v[0] <= 16 && s->cfg.v[1] <= 16;   /* (the kernel's step table) */
-    if ((s->cfg.fuse & 512) && ((s->cfg.ksp_type == MG_KSP_RICHARDSON && s->cfg.v[0] >= 1) || cheby_tail)) {
+    if ((s->cfg.fuse & MG_FUSE_LDS_TAIL) && ((s->cfg.ksp_type == MG_KSP_RICHARDSON && s->cfg.v[0] >= 1) || cheby_tail)) {
         for (int l = (s->ldist > 0 ? s->ldist : 1); l < s->levels; l++)
             if (s->L[l].n <= mgk_tail_max_n(cfg->dim)) { s->ltail = l; break; }
         if (s->ltail && (s->levels - s->ltail < 2 || s->levels - s->ltail > 8)) s->ltail = 0;
@@ -629,6 +636,8 @@ static void *prof_begin(mg_solver *s, int level) {
     mgk_timer_start(s->ctx, t, NULL);
     return t;
 }
+/* the same for a launch of another kind (mg_solver_profile_read_kind); the kind of the next timer goes back to 0, the plain sweep */
+static void *prof_begin_kind(mg_solver *s, int level, int kind) { s->prof_kind = kind; void *t = prof_begin(s, level); s->prof_kind = 0; return t; }
 static void prof_end(mg_solver *s, void *t) { if (t) mgk_timer_stop(s->ctx, t, NULL); }
 
 int mg_solver_profile(mg_solver *s, int enable) { s->prof_on = enable; s->prof_n = 0; return 0; }
@@ -708,7 +717,7 @@ static int smooth_chebyshev(mg_solver *s, int l, int maxit) {
      * solve still makes that one step (round 3: the product returned the guess untouched -- found by the random draws over the mock) */
     if (!F->guess_nonzero) {
         CHK(mgk_memset0(s->ctx, pkm1, bytes, NULL));
-        F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+        mgi_u_rewritten(F);
         if (mesh) CHK(mgk_jacobi_zero_rowcoef_f64(s->ctx, &F->g, L->dtab, scale, (const double *)F->b, pk, NULL));
         else CHK(mgk_jacobi_zero_f64(s->ctx, &F->g, L->dinv, scale, (const double *)F->b, pk, NULL));
     } else {
@@ -727,8 +736,20 @@ static int smooth_chebyshev(mg_solver *s, int l, int maxit) {
         double *t = pkm1; pkm1 = pk; pk = pkp1; pkp1 = t;
     }
     F->u = pk; F->tmp = pkm1; L->p2 = pkp1;
-    F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+    mgi_u_rewritten(F);
     return 0;
+}
+
+/* the coarse landing of the distributed level l - 1: the geometry of the planes of level l that this rank's restriction produces (*gc) and
+ * where they go in level l's b.  Level l distributed: its own slab.  Slab -> replicated: my planes [zstart[me], zstart[me + 1]) of the whole
+ * field, in place; the caller all-gathers them afterwards */
+static void *coarse_landing(const mg_solver *s, int P, int l, mgk_geom *gc) {
+    const mg_fset *Cq = &s->L[l].f[P];
+    *gc = Cq->g;
+    if (s->L[l].distributed) return Cq->b;
+    const int me = s->cfg.rank, c0 = s->zstart[me], c1 = s->zstart[me + 1];
+    gc->nz = c1 - c0;
+    return (char *)Cq->b + (size_t)OPS[P].esz * (size_t)c0 * (size_t)Cq->g.plane;
 }
 
 /* KSPSolve(ksp[l], b[l], u[l]) with KSP_NORM_NONE and max_it = maxit (src/solver.c:1465-1509) */
@@ -736,7 +757,7 @@ static int smooth_chebyshev(mg_solver *s, int l, int maxit) {
  * fuse bit 10): fp64, whole 3-D grids of full-row shape.  Not when that restriction is the first kernel of the coarse-level graph while
  * this level's sweeps run outside it (the replayed kernel would keep the buffers of the recording cycle; the swap is made on the host) */
 static int srr_ok(const mg_solver *s, int P, int l) {
-    if (!(s->cfg.fuse & 1024) || P != 0 || s->cfg.ksp_type != MG_KSP_RICHARDSON) return 0;
+    if (!(s->cfg.fuse & MG_FUSE_SWEEP_RESTRICT) || P != 0 || s->cfg.ksp_type != MG_KSP_RICHARDSON) return 0;
     if (l + 1 >= s->levels || (s->lgraph && l + 1 == s->lgraph)) return 0;
     /* 2-D (mgk_sweep_residual_restrict_2d_f64, any grid): from 2047^2 on; on the smaller levels of the 4097^2 cycle its marching waves
      * take 15-20 us where a short sweep and the short fused restriction take 5 + 10 (MG_SRR2D_MIN_N overrides, for tests) */
@@ -747,8 +768,7 @@ static int srr_ok(const mg_solver *s, int P, int l) {
     if (s->L[l].distributed) {
         /* z-slab: the neighbours' planes arrive in ONE grouped exchange (u and b ghosts, far, far2, bfar) */
         const mg_fset *F = &s->L[l].f[0];
-        mgk_geom gc = s->L[l + 1].f[0].g;
-        if (!s->L[l + 1].distributed) gc.nz = s->zstart[s->cfg.rank + 1] - s->zstart[s->cfg.rank];
+        mgk_geom gc; coarse_landing(s, 0, l + 1, &gc);
         return F->far && F->far2 && F->bfar && s->L[l].nz_min >= 6 && mgk_sweep_residual_restrict_slab_ok_f64(&F->g, &gc);
     }
     return mgk_sweep_residual_restrict_ok_f64(&s->L[l].f[0].g, &s->L[l + 1].f[0].g);
@@ -768,23 +788,23 @@ static int srr_ok(const mg_solver *s, int P, int l) {
  * from the builds that link this file against a stand-in of the kernel ABI: the references are weak, and without it everything below
  * runs step by step as before */
 static int cheby_fused(const mg_solver *s) {
-    return s->cfg.ksp_type == MG_KSP_CHEBYSHEV && (s->cfg.fuse & 32768) && mg_cheby_pass && mg_cheby_tail &&
+    return s->cfg.ksp_type == MG_KSP_CHEBYSHEV && (s->cfg.fuse & MG_FUSE_CHEBY) && mg_cheby_pass && mg_cheby_tail &&
            s->cfg.precision == MG_PREC_FP64 && s->cfg.nranks == 1;
 }
 static int j3_2d_ok(const mg_solver *s, int P, int l, int maxit) {
-    if (!(s->cfg.fuse & 8192) || s->cfg.dim != 2 || P != 0 || s->L[l].distributed) return 0;
+    if (!(s->cfg.fuse & MG_FUSE_TRIPLE_2D) || s->cfg.dim != 2 || P != 0 || s->L[l].distributed) return 0;
     if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV) return maxit == 3 && cheby_fused(s);
     return maxit >= 3;
 }
 /* Chebyshev: does level l ever run smooth_chebyshev (which rotates u, tmp and p2)?  Not inside the tail kernel, not on the three-step passes */
 static int cheby_steps_by_launch(const mg_solver *s, int l) {
     if (s->ltail && l >= s->ltail) return 0;
-    return !j3_2d_ok(s, 0, l, (l == s->levels - 1 && s->levels > 1) ? s->cfg.v[1] : s->cfg.v[0]);
+    return !j3_2d_ok(s, 0, l, level_sweeps(s, l));
 }
 static int triple_ok(const mg_solver *s, int P, int l, int maxit) {
     const mg_level *L = &s->L[l];
     if (j3_2d_ok(s, P, l, maxit)) return 1;
-    if (!(s->cfg.fuse & 2048) || !(s->cfg.fuse & 32) || s->cfg.ksp_type != MG_KSP_RICHARDSON || s->cfg.dim != 3 || s->cfg.mesh) return 0;
+    if (!(s->cfg.fuse & MG_FUSE_ZERO_TRIPLE) || !(s->cfg.fuse & MG_FUSE_PAIRS) || s->cfg.ksp_type != MG_KSP_RICHARDSON || s->cfg.dim != 3 || s->cfg.mesh) return 0;
     if (maxit < 3 || L->distributed || L->n < s->cfg.pair_min_n || L->n + 1 > 1024) return 0;
     return P == 0 ? mgk_jacobi2_zero_ok_f64(&L->f[0].g) : mgk_jacobi2_zero_ok_f32(&L->f[1].g);
 }
@@ -794,7 +814,7 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
     if (s->cfg.pc_type == MG_PC_LINE_Y) {                           /* y-line Jacobi: every sweep in place (mg_line.c), no swap, no flag */
         mg_fset *Fl = &s->L[l].f[0];
         Fl->pre_done = 0; Fl->jz_ready = 0; Fl->last_sweep_pending = 0;
-        Fl->u_ghost_ok = 0; Fl->u_ghost_pending = 0;
+        mgi_u_rewritten(Fl);
         return mg_line_smooth(s, l, maxit);
     }
     if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV && !j3_2d_ok(s, P, l, maxit)) return smooth_chebyshev(s, l, maxit);
@@ -803,7 +823,7 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
     const mg_ops *O = &OPS[P];
     if (maxit == 0 && !F->guess_nonzero) {                          /* KSPSolve zero-fills */
         CHK(mgk_memset0(s->ctx, F->u, (size_t)O->esz * (size_t)F->g.total, NULL));
-        F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+        mgi_u_rewritten(F);
     }
     int it0 = 0;
     F->last_sweep_pending = 0;
@@ -815,7 +835,7 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
     if (l == 0 && P == 0 && s->spec_valid && maxit >= s->spec_valid && F->guess_nonzero) {
         /* the first sweep(s) were already made by the kernel that evaluated the previous cycle's residual norm */
         swap_ptr(&F->u, &F->tmp);
-        F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+        mgi_u_rewritten(F);
         it0 = s->spec_valid;
         s->spec_valid = 0;
         s->iterate_behind = 0;              /* (u is now the sweep AFTER the iterate the last norm belongs to) */
@@ -825,7 +845,7 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
      * the coarse-level HIP graph refers to: pre- and post-smoothing group their v0 sweeps in the same way (one launch for the
      * first sweep -- zero guess / fused prolongation / adopted speculative sweep -- then pairs), so a level swaps u/tmp the
      * same number of times on the way down and on the way up: an even count per cycle, the pointers the graph recorded stay valid */
-    const int pair_ok = (s->cfg.fuse & 32) && L->n >= s->cfg.pair_min_n &&
+    const int pair_ok = (s->cfg.fuse & MG_FUSE_PAIRS) && L->n >= s->cfg.pair_min_n &&
                         ((s->cfg.dim == 3 && L->n + 1 <= 1024 && (!L->distributed || (F->far && L->nz_min >= 4))) ||
                          (s->cfg.dim == 2 && P == 0));
     if (maxit < 1 || F->guess_nonzero) F->jz_ready = 0;
@@ -838,13 +858,11 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
              * pointers the coarse-level graph recorded stay valid */
             if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV) CHK(mg_cheby_pass(s, l, F->guess_nonzero ? MG_CHEBY_PLAIN : MG_CHEBY_ZERO, NULL));
             else if (!F->guess_nonzero)
-                CHK(mgk_jacobi3_2d_zero_f64(s->ctx, &F->g, mesh ? NULL : L->coef, mesh ? 1.0 : L->dinv, s->cfg.scale, mesh ? L->ctab : NULL,
-                                            mesh ? L->dtab : NULL, (const double *)F->b, (double *)F->tmp, NULL));
+                CHK(mgk_jacobi3_2d_zero_f64(s->ctx, &F->g, J3_COEFS(L), (const double *)F->b, (double *)F->tmp, NULL));
             else
-                CHK(mgk_jacobi3_2d_f64(s->ctx, &F->g, mesh ? NULL : L->coef, mesh ? 1.0 : L->dinv, s->cfg.scale, mesh ? L->ctab : NULL,
-                                       mesh ? L->dtab : NULL, (const double *)F->b, (const double *)F->u, (double *)F->tmp, NULL));
+                CHK(mgk_jacobi3_2d_f64(s->ctx, &F->g, J3_COEFS(L), (const double *)F->b, (const double *)F->u, (double *)F->tmp, NULL));
             swap_ptr(&F->u, &F->tmp);
-            F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+            mgi_u_rewritten(F);
             it += 2;
             continue;
         }
@@ -853,7 +871,7 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
              * two swaps of the zero-guess sweep and the pair it replaces cancel, the pointers the coarse-level graph holds stay valid) */
             if (P == 0) CHK(mgk_jacobi2_zero_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (double *)F->u, NULL));
             else CHK(mgk_jacobi2_zero_f32(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const float *)F->b, (float *)F->u, NULL));
-            F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+            mgi_u_rewritten(F);
             it += 2;
             continue;
         }
@@ -877,9 +895,7 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
                 CHK(group_exchange(s, P, F, 0));
                 /* ... while the planes 2 .. nz-3, which need no ghost data, are already being swept */
                 if (s->cfg.overlap && L->nz_min >= 6) {
-                    s->prof_kind = 1;                       /* timed: the interior planes 2 .. nz-3 of the slab */
-                    void *t = prof_begin(s, l);
-                    s->prof_kind = 0;
+                    void *t = prof_begin_kind(s, l, 1);     /* timed: the interior planes 2 .. nz-3 of the slab */
                     CHK(O->jacobi2_slab(s->ctx, &F->g, &F->gfar, L->coef, L->dinv, s->cfg.scale, F->b, F->u, F->tmp, F->far, lo, hi, 2, nz - 2, cs));
                     prof_end(s, t);
                 }
@@ -892,18 +908,14 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
                     CHK(O->jacobi2_slab(s->ctx, &F->g, &F->gfar, L->coef, L->dinv, s->cfg.scale, F->b, F->u, F->tmp, F->far, lo, hi, 0, nz, cs));
                 }
             } else if (s->cfg.dim == 2) {
-                s->prof_kind = 1;
-                void *t = prof_begin(s, l);
-                s->prof_kind = 0;
+                void *t = prof_begin_kind(s, l, 1);
                 if (mesh) CHK(mgk_jacobi2_2d_rowcoef_f64(s->ctx, &F->g, L->ctab, L->dtab, s->cfg.scale, (const double *)F->b,
                                                          (const double *)F->u, (double *)F->tmp, NULL));
                 else CHK(mgk_jacobi2_2d_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u,
                                             (double *)F->tmp, NULL));
                 prof_end(s, t);
             } else {
-                s->prof_kind = 1;
-                void *t = prof_begin(s, l);
-                s->prof_kind = 0;
+                void *t = prof_begin_kind(s, l, 1);
                 CHK(O->jacobi2(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, F->b, F->u, F->tmp, NULL));
                 prof_end(s, t);
             }
@@ -932,7 +944,7 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
                                      F->g.dim == 3 ? F->g.nz : F->g.ny, NULL));
             prof_end(s, t);
         }
-        F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+        mgi_u_rewritten(F);
         swap_ptr(&F->u, &F->tmp);
     }
     return 0;
@@ -1040,7 +1052,7 @@ static int prolong_from(mg_solver *s, int P, int l) {
  * iterate the norm belongs to is never stored: if the iteration stops, finalize_iterate() makes that one sweep. */
 static int pjp_ok(const mg_solver *s, int P) {
     const mg_level *L = &s->L[0];
-    const int need = 4096 | 1024 | 32 | 8 | 2 | 1;
+    const int need = MG_FUSE_PROLONG_PAIR | MG_FUSE_SWEEP_RESTRICT | MG_FUSE_PAIRS | MG_FUSE_NORM_SWEEP | MG_FUSE_PROLONG_SWEEP | MG_FUSE_RESNORM;
     if ((s->cfg.fuse & need) != need || P != 0 || s->cfg.dim != 3 || s->cfg.mesh || s->cfg.ksp_type != MG_KSP_RICHARDSON) return 0;
     if (s->cfg.v[0] != 3 || s->levels < 2 || s->lgraph == 1 || L->n < s->cfg.pair_min_n || s->last_cycle) return 0;
     if (L->distributed) {
@@ -1048,7 +1060,7 @@ static int pjp_ok(const mg_solver *s, int P) {
          * planes of u (before the correction) and of the coarse u -- the far fields of the two-sweep passes of both levels carry them */
         const mg_level *Lc = &s->L[1];
         const int hi = s->cfg.rank < s->cfg.nranks - 1;
-        if (!(s->cfg.fuse & 16384) || !Lc->distributed || !L->f[0].far || !Lc->f[0].far || L->nz_min < 8 || Lc->nz_min < 4) return 0;
+        if (!(s->cfg.fuse & MG_FUSE_PROLONG_PAIR_SLAB) || !Lc->distributed || !L->f[0].far || !Lc->f[0].far || L->nz_min < 8 || Lc->nz_min < 4) return 0;
         return mgk_prolong_jacobi2_slab_ok_f64(&L->f[0].g, &Lc->f[0].g, hi) && mgk_jacobi2_sumsq_ok_f64(&L->f[0].g);
     }
     return mgk_prolong_jacobi2_ok_f64(&L->f[0].g, &s->L[1].f[0].g) && mgk_jacobi2_sumsq_ok_f64(&L->f[0].g);
@@ -1063,7 +1075,7 @@ static int finalize_iterate(mg_solver *s) {
     } else
     CHK(mgk_jacobi_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u, (double *)F->tmp, NULL));
     swap_ptr(&F->u, &F->tmp);
-    F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+    mgi_u_rewritten(F);
     s->iterate_behind = 0; s->spec_valid = 0;
     return 0;
 }
@@ -1074,7 +1086,7 @@ static int prolong_smooth(mg_solver *s, int P, int l) {
     mg_fset *F = &Lf->f[P], *Cq = &Lc->f[P];
     const mg_ops *O = &OPS[P];
     const int v0 = s->cfg.v[0];
-    if (!(s->cfg.fuse & 2) || (s->cfg.ksp_type != MG_KSP_RICHARDSON && !j3_2d_ok(s, P, l, v0)) || v0 < 1) {
+    if (!(s->cfg.fuse & MG_FUSE_PROLONG_SWEEP) || (s->cfg.ksp_type != MG_KSP_RICHARDSON && !j3_2d_ok(s, P, l, v0)) || v0 < 1) {
         CHK(prolong_from(s, P, l));
         return smooth(s, P, l, v0, 0);
     }
@@ -1083,10 +1095,10 @@ static int prolong_smooth(mg_solver *s, int P, int l) {
         const int mesh = s->cfg.mesh != 0;
         if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV) CHK(mg_cheby_pass(s, l, MG_CHEBY_PROLONG, NULL));
         else
-        CHK(mgk_prolong_jacobi3_2d_f64(s->ctx, &F->g, &Cq->g, mesh ? NULL : Lf->coef, mesh ? 1.0 : Lf->dinv, s->cfg.scale, mesh ? Lf->ctab : NULL,
-                                       mesh ? Lf->dtab : NULL, (const double *)F->b, (const double *)Cq->u, (const double *)F->u, (double *)F->tmp, NULL));
+        CHK(mgk_prolong_jacobi3_2d_f64(s->ctx, &F->g, &Cq->g, J3_COEFS(Lf), (const double *)F->b, (const double *)Cq->u, (const double *)F->u,
+                                       (double *)F->tmp, NULL));
         swap_ptr(&F->u, &F->tmp);
-        F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+        mgi_u_rewritten(F);
         return v0 > 3 ? smooth(s, P, l, v0 - 3, 0) : 0;
     }
     if (l == 0 && pjp_ok(s, P) && Lf->distributed) {
@@ -1118,7 +1130,7 @@ static int prolong_smooth(mg_solver *s, int P, int l) {
         } else CHK(PJ2S(0, nz));
 #undef PJ2S
         swap_ptr(&F->u, &F->tmp);
-        F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+        mgi_u_rewritten(F);
         s->sweep_owed = 1;
         return 0;
     }
@@ -1128,7 +1140,7 @@ static int prolong_smooth(mg_solver *s, int P, int l) {
         CHK(mgk_prolong_jacobi2_f64(s->ctx, &F->g, &Cq->g, Lf->coef, Lf->dinv, s->cfg.scale, (const double *)F->b, (const double *)Cq->u,
                                     (const double *)F->u, (double *)F->tmp, NULL));
         swap_ptr(&F->u, &F->tmp);
-        F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+        mgi_u_rewritten(F);
         s->sweep_owed = 1;
         return 0;
     }
@@ -1160,7 +1172,7 @@ static int prolong_smooth(mg_solver *s, int P, int l) {
         else CHK(O->prolong_jacobi(s->ctx, &F->g, &gc, Lf->coef, Lf->dinv, s->cfg.scale, F->b, ucoarse, F->u, F->tmp, NULL));
     }
     swap_ptr(&F->u, &F->tmp);
-    F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+    mgi_u_rewritten(F);
     return smooth(s, P, l, v0 - 1, 0);
 }
 
@@ -1195,20 +1207,29 @@ static int tail(mg_solver *s, int P) {
 
 /* one step of the descent: b_l = R(b_{l-1} - A u_{l-1}); smooth level l from a zero guess (src/solver.c:1534-1537) */
 static int descend(mg_solver *s, int P, int l) {
-    const int levels = s->levels, *v = s->cfg.v;
+    const int levels = s->levels;
     if (s->ltail && l == s->ltail) {              /* the restriction feeds the tail kernel, which smooths this level and all below */
         CHK(descend_restrict(s, P, l, 1));
         return tail(s, P);
     }
     CHK(descend_restrict(s, P, l, 0));
-    CHK(smooth(s, P, l, l == levels - 1 ? v[1] : v[0], l != levels - 1));   /* :1536 */
+    CHK(smooth(s, P, l, level_sweeps(s, l), l != levels - 1));            /* :1536 */
     if (l != levels - 1) s->L[l].f[P].guess_nonzero = 1;                /* :1537 */
     return 0;
 }
 
+/* fuse bit 8: does the pass that writes b_l (the restriction from level l - 1) also write level l's first sweep from the zero guess, into tmp?
+ * Where level l is smoothed by its own launches (no_jz: it is the tail kernel's), by Richardson, at least once, from the zero guess, and does
+ * not open with the three-sweep pass over b alone.  descend_restrict asks this in three places; the one behind last_sweep_pending used to
+ * leave the ksp_type test out, which is the same thing: that flag is set in smooth() under srr_ok() alone, and srr_ok() requires Richardson */
+static int coarse_zero_sweep_ok(const mg_solver *s, int P, int l, int no_jz) {
+    const int sweeps = level_sweeps(s, l);
+    return (s->cfg.fuse & MG_FUSE_COARSE_ZERO_SWEEP) && !no_jz && s->cfg.ksp_type == MG_KSP_RICHARDSON && sweeps >= 1 &&
+           !s->L[l].f[P].guess_nonzero && !triple_ok(s, P, l, sweeps);
+}
+
 /* b_l = R(b_{l-1} - A u_{l-1})  (src/solver.c:1534-1535) */
 static int descend_restrict(mg_solver *s, int P, int l, int no_jz) {
-    const int levels = s->levels, *v = s->cfg.v;
     mg_level *Lf = &s->L[l - 1];
     const mg_ops *O = &OPS[P];
     if (Lf->f[P].last_sweep_pending && Lf->distributed) {
@@ -1220,14 +1241,9 @@ static int descend_restrict(mg_solver *s, int P, int l, int no_jz) {
         mg_fset *F = &Lf->f[P], *Cq = &Lc->f[P];
         void *cs = mgk_stream_compute(s->ctx), *ms = mgk_stream_comm(s->ctx);
         const int me = s->cfg.rank, lo = me > 0, hi = me < s->cfg.nranks - 1;
-        mgk_geom gc = Cq->g;
-        void *bc = Cq->b;
+        mgk_geom gc;                            /* (slab -> replicated: my coarse planes land in place, then all-gather) */
+        void *bc = coarse_landing(s, P, l, &gc);
         Cq->b_ghost_ok = 0; Cq->bfar_ok = 0;
-        if (!Lc->distributed) {                 /* slab -> replicated: my coarse planes land in place, then all-gather */
-            const int c0 = s->zstart[me], c1 = s->zstart[me + 1];
-            gc.nz = c1 - c0;
-            bc = (char *)Cq->b + (size_t)O->esz * (size_t)c0 * (size_t)Cq->g.plane;
-        }
         const int nzc = gc.nz;
         CHK(group_exchange(s, P, F, 1));
         /* coarse planes 1 .. nzc-3 read the fine planes 0 .. nz-2 of u only */
@@ -1240,7 +1256,7 @@ static int descend_restrict(mg_solver *s, int P, int l, int no_jz) {
         else CHK(SRRS(0, nzc));
 #undef SRRS
         swap_ptr(&F->u, &F->tmp);
-        F->u_ghost_ok = 0; F->u_ghost_pending = 0; F->b_ghost_ok = 1; F->bfar_ok = 1; F->last_sweep_pending = 0;
+        mgi_u_rewritten(F); F->b_ghost_ok = 1; F->bfar_ok = 1; F->last_sweep_pending = 0;
         if (!Lc->distributed) {
             CHK(mgk_stream_wait(s->ctx, ms, cs));
             CHK(s->comm->allgather_planes(s->comm, s->ctx, Cq->b, &Cq->g, s->zstart, O->esz, ms));
@@ -1251,8 +1267,7 @@ static int descend_restrict(mg_solver *s, int P, int l, int no_jz) {
     if (Lf->f[P].last_sweep_pending) {
         /* the last pre-smoothing sweep, the residual and its restriction in one pass (:1531 / :1536 last iteration, :1534-1535) */
         mg_fset *F = &Lf->f[P], *Cq = &s->L[l].f[P];
-        const int sweeps = (l == levels - 1) ? v[1] : v[0];
-        const int jz = (s->cfg.fuse & 256) && !no_jz && sweeps >= 1 && !Cq->guess_nonzero && !triple_ok(s, P, l, sweeps);
+        const int jz = coarse_zero_sweep_ok(s, P, l, no_jz);
         if (s->cfg.mesh)
             CHK(mgk_sweep_residual_restrict_2d_rowcoef_f64(s->ctx, &F->g, &Cq->g, Lf->ctab, Lf->dtab, s->cfg.scale, (const double *)F->b, (const double *)F->u,
                                                            (double *)F->tmp, (double *)Cq->b, jz ? (double *)Cq->tmp : NULL, s->L[l].dtab, s->cfg.scale, NULL));
@@ -1263,18 +1278,17 @@ static int descend_restrict(mg_solver *s, int P, int l, int no_jz) {
         CHK(mgk_sweep_residual_restrict_f64(s->ctx, &F->g, &Cq->g, Lf->coef, Lf->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u,
                                             (double *)F->tmp, (double *)Cq->b, jz ? (double *)Cq->tmp : NULL, s->L[l].dinv, s->cfg.scale, NULL));
         swap_ptr(&F->u, &F->tmp);
-        F->u_ghost_ok = 0; F->u_ghost_pending = 0; F->last_sweep_pending = 0;
+        mgi_u_rewritten(F); F->last_sweep_pending = 0;
         Cq->b_ghost_ok = 0; Cq->bfar_ok = 0;
         if (jz) Cq->jz_ready = 1;
         return 0;
     }
     /* (below 255^3 the marching fused kernel is latency bound: residual + restriction as two short kernels are quicker) */
-    if ((s->cfg.fuse & 4) && O->residual_restrict && s->cfg.dim == 3 && !Lf->distributed && Lf->n + 1 <= 1024 &&
-        (Lf->n >= 255 || (s->cfg.fuse & 128))) {
+    if ((s->cfg.fuse & MG_FUSE_RES_RESTRICT) && O->residual_restrict && s->cfg.dim == 3 && !Lf->distributed && Lf->n + 1 <= 1024 &&
+        (Lf->n >= 255 || (s->cfg.fuse & MG_FUSE_RES_RESTRICT_SMALL))) {
         /* :1534-1535 in one pass: b_l = R (b - A u), the fine residual is never written */
         mg_fset *Cq = &s->L[l].f[P];
-        const int sweeps = (l == levels - 1) ? v[1] : v[0];
-        if ((s->cfg.fuse & 256) && !no_jz && s->cfg.ksp_type == MG_KSP_RICHARDSON && sweeps >= 1 && !Cq->guess_nonzero && !triple_ok(s, P, l, sweeps)) {
+        if (coarse_zero_sweep_ok(s, P, l, no_jz)) {
             /* ... and the coarse level's first sweep from its zero guess comes out of the same kernel (saves re-reading b_l) */
             CHK(O->residual_restrict_jz(s->ctx, &Lf->f[P].g, &Cq->g, Lf->coef, Lf->f[P].b, Lf->f[P].u, Cq->b, Cq->tmp, s->L[l].dinv,
                                         s->cfg.scale, NULL));
@@ -1282,7 +1296,7 @@ static int descend_restrict(mg_solver *s, int P, int l, int no_jz) {
         } else {
             CHK(O->residual_restrict(s->ctx, &Lf->f[P].g, &Cq->g, Lf->coef, Lf->f[P].b, Lf->f[P].u, Cq->b, NULL));
         }
-    } else if ((s->cfg.fuse & 4) && O->residual_restrict && s->cfg.dim == 3 && Lf->distributed && Lf->n + 1 <= 1024 &&
+    } else if ((s->cfg.fuse & MG_FUSE_RES_RESTRICT) && O->residual_restrict && s->cfg.dim == 3 && Lf->distributed && Lf->n + 1 <= 1024 &&
                Lf->nz_min >= 2) {
         /* the same on a z-slab.  The last coarse plane of every rank but the last needs the residual of the NEXT rank's
          * first plane: each rank evaluates that one plane first and ships it (comm stream) while the fused kernel
@@ -1293,13 +1307,8 @@ static int descend_restrict(mg_solver *s, int P, int l, int no_jz) {
         void *cs = mgk_stream_compute(s->ctx), *ms = mgk_stream_comm(s->ctx);
         const int me = s->cfg.rank, last = (me == s->cfg.nranks - 1);
         Cq->b_ghost_ok = 0; Cq->bfar_ok = 0;
-        mgk_geom gc = Cq->g;
-        void *bc = Cq->b;
-        if (!Lc->distributed) {                 /* slab -> replicated: my coarse planes land in place, then all-gather */
-            const int c0 = s->zstart[me], c1 = s->zstart[me + 1];
-            gc.nz = c1 - c0;
-            bc = (char *)Cq->b + (size_t)O->esz * (size_t)c0 * (size_t)Cq->g.plane;
-        }
+        mgk_geom gc;                            /* (slab -> replicated: my coarse planes land in place, then all-gather) */
+        void *bc = coarse_landing(s, P, l, &gc);
         if (F->far && Lf->nz_min >= 4) {
             /* ONE exchange: with u's and b's ghost planes and the neighbours' second planes of u (the far field of the two-sweep
              * passes) every rank evaluates the residual of the plane above its slab itself and completes its last coarse plane.
@@ -1345,12 +1354,11 @@ gathered:
             CHK(s->comm->allgather_planes(s->comm, s->ctx, Cq->b, &Cq->g, s->zstart, O->esz, ms));
             CHK(mgk_stream_wait(s->ctx, cs, ms));
         }
-    } else if ((s->cfg.fuse & 4) && s->cfg.dim == 2 && P == 0 && Lf->n >= 127) {
+    } else if ((s->cfg.fuse & MG_FUSE_RES_RESTRICT) && s->cfg.dim == 2 && P == 0 && Lf->n >= 127) {
         /* 2-D: the same fusion, one independent wave per tile (mgk_residual_restrict_2d_f64), with the coarse level's first
          * zero-guess sweep when that level is smoothed by its own launches */
         mg_fset *Cq = &s->L[l].f[P];
-        const int sweeps = (l == levels - 1) ? v[1] : v[0];
-        const int jz = (s->cfg.fuse & 256) && !no_jz && s->cfg.ksp_type == MG_KSP_RICHARDSON && sweeps >= 1 && !Cq->guess_nonzero && !triple_ok(s, P, l, sweeps);
+        const int jz = coarse_zero_sweep_ok(s, P, l, no_jz);
         if (s->cfg.mesh) CHK(mgk_residual_restrict_2d_rowcoef_f64(s->ctx, &Lf->f[P].g, &Cq->g, Lf->ctab, (const double *)Lf->f[P].b,
                                                                   (const double *)Lf->f[P].u, (double *)Cq->b, jz ? (double *)Cq->tmp : NULL,
                                                                   s->L[l].dtab, s->cfg.scale, NULL));
@@ -1432,8 +1440,8 @@ static int vcycle_once(mg_solver *s) {
         CHK(cycle_body(s, 1, 1));
         /* the fp32 cycle that follows starts from e = 0: its first sweep, scale * (r32 * dinv), comes out of the same pass that
          * produces r32 (fuse bit 8): one launch and one read of r32 less per outer step */
-        const int jz = (s->cfg.fuse & 256) && s->cfg.v[0] >= 1 && s->levels > 1 && !triple_ok(s, 1, 0, s->cfg.v[0]);
-        if ((s->cfg.fuse & 16) && F->tmp && !L->distributed) {
+        const int jz = (s->cfg.fuse & MG_FUSE_COARSE_ZERO_SWEEP) && s->cfg.v[0] >= 1 && s->levels > 1 && !triple_ok(s, 1, 0, s->cfg.v[0]);
+        if ((s->cfg.fuse & MG_FUSE_MIXED_CORRECT) && F->tmp && !L->distributed) {
             /* u += (double) e and r32 = (float)(b - A u) in one pass (32 B/unknown instead of 20 + 20) */
             if (jz) CHK(mgk_correct_residual_f64_f32_jz(s->ctx, &F->g, &E->g, L->coef, (const double *)F->b, (const double *)F->u,
                                                         (const float *)E->u, (double *)F->tmp, (float *)E->b, (float *)E->tmp, L->dinv,
@@ -1441,10 +1449,10 @@ static int vcycle_once(mg_solver *s) {
             else CHK(mgk_correct_residual_f64_f32(s->ctx, &F->g, &E->g, L->coef, (const double *)F->b, (const double *)F->u,
                                                   (const float *)E->u, (double *)F->tmp, (float *)E->b, &ss, NULL));
             swap_ptr(&F->u, &F->tmp);
-            F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+            mgi_u_rewritten(F);
         } else {
             CHK(mgk_correct_f64_from_f32(s->ctx, &F->g, &E->g, (const float *)E->u, (double *)F->u, NULL));
-            F->u_ghost_ok = 0; F->u_ghost_pending = 0;
+            mgi_u_rewritten(F);
             CHK(ensure_u_ghosts(s, 0, L));
             if (jz) CHK(mgk_residual_f64_to_f32_jz(s->ctx, &F->g, &E->g, L->coef, (const double *)F->b, (const double *)F->u, (float *)E->b,
                                                    (float *)E->tmp, L->dinv, s->cfg.scale, &ss, NULL));
@@ -1455,7 +1463,7 @@ static int vcycle_once(mg_solver *s) {
     } else {
         CHK(cycle_body(s, 0, s->iter == 0));
         /* :1545-1546  r0 = b0 - A0 u0 ; ||r0|| */
-        const int jnorm = (s->cfg.fuse & 8) && (s->cfg.fuse & 1) && (s->cfg.ksp_type == MG_KSP_RICHARDSON || j3_2d_ok(s, 0, 0, s->cfg.v[0])) &&
+        const int jnorm = (s->cfg.fuse & MG_FUSE_NORM_SWEEP) && (s->cfg.fuse & MG_FUSE_RESNORM) && (s->cfg.ksp_type == MG_KSP_RICHARDSON || j3_2d_ok(s, 0, 0, s->cfg.v[0])) &&
                           s->cfg.v[0] >= 1 && !s->last_cycle;
         if (s->sweep_owed && L->distributed) {
             /* ... on a z-slab: the planes 2 .. nz-3 while the grouped exchange (u's ghosts, the far planes; b's are valid) travels, one reduction
@@ -1468,9 +1476,7 @@ static int vcycle_once(mg_solver *s) {
                                 (double *)F->tmp, (const double *)F->far, lo, hi, z0, z1, off, np, cs)
             const int split = s->cfg.overlap && nz >= 6;
             if (split) {
-                s->prof_kind = 1;
-                void *t = prof_begin(s, 0);
-                s->prof_kind = 0;
+                void *t = prof_begin_kind(s, 0, 1);
                 int rc2 = J2M(2, nz - 2, 0, &n1);
                 prof_end(s, t);
                 CHK(rc2);
@@ -1487,9 +1493,7 @@ static int vcycle_once(mg_solver *s) {
         if (s->sweep_owed) {
             /* the third post-smoothing sweep, the norm of ITS result and the first pre-smoothing sweep of the next cycle in one pass;
              * u stays one sweep behind the iterate, tmp is one sweep ahead of it */
-            s->prof_kind = 1;
-            void *t = prof_begin(s, 0);
-            s->prof_kind = 0;
+            void *t = prof_begin_kind(s, 0, 1);
             int rc2 = mgk_jacobi2_sumsq_mid_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u,
                                                 (double *)F->tmp, &ss, NULL);
             prof_end(s, t);
@@ -1497,7 +1501,7 @@ static int vcycle_once(mg_solver *s) {
             s->sweep_owed = 0; s->iterate_behind = 1; s->spec_valid = 1;
             goto norm_done;
         }
-        if (jnorm && L->distributed && s->cfg.dim == 3 && (s->cfg.fuse & 1024) && (s->cfg.fuse & 32) && F->far && L->nz_min >= 6 &&
+        if (jnorm && L->distributed && s->cfg.dim == 3 && (s->cfg.fuse & MG_FUSE_SWEEP_RESTRICT) && (s->cfg.fuse & MG_FUSE_PAIRS) && F->far && L->nz_min >= 6 &&
             s->cfg.v[0] >= 2 && L->n >= s->cfg.pair_min_n && L->n + 1 <= 1024 && s->lgraph != 1 && mgk_jacobi2_sumsq_ok_f64(&F->g)) {
             /* slab: the norm and the first TWO sweeps of the next cycle in one pass (the two-sweep slab pass with the norm of its
              * input's residual): the planes 2 .. nz-3 while the grouped exchange (u's ghosts, b's once, the far planes) travels */
@@ -1542,17 +1546,14 @@ static int vcycle_once(mg_solver *s) {
              * cycle follows; u itself is untouched, so stopping here leaves the solution as the reference has it. */
             /* (not when level 0 feeds the coarse-level graph: adopting two sweeps at once changes how often level 0 swaps u / tmp in
              * a cycle from the recording cycle's count, and the recorded restriction reads level 0's buffers) */
-            const int two = (s->cfg.fuse & 1024) && (s->cfg.fuse & 32) && !L->distributed &&
+            const int two = (s->cfg.fuse & MG_FUSE_SWEEP_RESTRICT) && (s->cfg.fuse & MG_FUSE_PAIRS) && !L->distributed &&
                             s->cfg.v[0] >= 2 && L->n >= s->cfg.pair_min_n && s->lgraph != 1 && (s->cfg.dim == 2 || mgk_jacobi2_sumsq_ok_f64(&F->g));
             if (j3_2d_ok(s, 0, 0, s->cfg.v[0])) {
                 /* 2-D: ... and ALL THREE pre-smoothing sweeps of the next cycle */
                 const int mesh = s->cfg.mesh != 0;
-                s->prof_kind = 1;
-                void *t = prof_begin(s, 0);
-                s->prof_kind = 0;
+                void *t = prof_begin_kind(s, 0, 1);
                 int rc2 = s->cfg.ksp_type == MG_KSP_CHEBYSHEV ? mg_cheby_pass(s, 0, MG_CHEBY_NORM, &ss) :
-                          mgk_jacobi3_2d_sumsq_f64(s->ctx, &F->g, mesh ? NULL : L->coef, mesh ? 1.0 : L->dinv, s->cfg.scale, mesh ? L->ctab : NULL,
-                                                   mesh ? L->dtab : NULL, (const double *)F->b, (const double *)F->u, (double *)F->tmp, &ss, NULL);
+                          mgk_jacobi3_2d_sumsq_f64(s->ctx, &F->g, J3_COEFS(L), (const double *)F->b, (const double *)F->u, (double *)F->tmp, &ss, NULL);
                 prof_end(s, t);
                 CHK(rc2);
                 s->spec_valid = 3;
@@ -1565,9 +1566,7 @@ static int vcycle_once(mg_solver *s) {
             else if (two && s->cfg.dim == 2) CHK(mgk_jacobi2_2d_sumsq_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b,
                                                                           (const double *)F->u, (double *)F->tmp, &ss, NULL));
             else if (two) {                                                             /* ... and the second one: two sweeps in the pass */
-                s->prof_kind = 1;                   /* timed with the two-sweep launches (same kernel + the per-block partial sums) */
-                void *t = prof_begin(s, 0);
-                s->prof_kind = 0;
+                void *t = prof_begin_kind(s, 0, 1); /* timed with the two-sweep launches (same kernel + the per-block partial sums) */
                 int rc2 = mgk_jacobi2_sumsq_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u,
                                                 (double *)F->tmp, &ss, NULL);
                 prof_end(s, t);
@@ -1576,9 +1575,9 @@ static int vcycle_once(mg_solver *s) {
             else CHK(mgk_jacobi_sumsq_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u,
                                           (double *)F->tmp, &ss, NULL));
             s->spec_valid = two ? 2 : 1;
-        } else if ((s->cfg.fuse & 1) && s->cfg.mesh)
+        } else if ((s->cfg.fuse & MG_FUSE_RESNORM) && s->cfg.mesh)
             CHK(mgk_residual_sumsq_rowcoef_f64(s->ctx, &F->g, L->ctab, (const double *)F->b, (const double *)F->u, &ss, NULL));
-        else if (s->cfg.fuse & 1) CHK(mgk_residual_sumsq_f64(s->ctx, &F->g, L->coef, (const double *)F->b, (const double *)F->u, &ss, NULL));
+        else if (s->cfg.fuse & MG_FUSE_RESNORM) CHK(mgk_residual_sumsq_f64(s->ctx, &F->g, L->coef, (const double *)F->b, (const double *)F->u, &ss, NULL));
         else {
             CHK(residual(s, 0, 0));
             CHK(mgk_sumsq_f64(s->ctx, &F->g, (const double *)F->rv, &ss, NULL));

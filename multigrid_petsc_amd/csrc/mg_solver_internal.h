@@ -13,6 +13,13 @@
 #define MG_MAX_LEVELS 32
 #define MG_MAX_TIMERS 4096
 
+/* fuse bits mg_solver_create clears (include/mgsolve.h: mg_fuse_bits) */
+/* y-line Jacobi: every pass that bakes POINT Jacobi into its kernel (bits 1, 3, 5, 8-15); the fused residual + norm and residual + restriction stay */
+#define MG_FUSE_POINT_JACOBI_PASSES (MG_FUSE_PROLONG_SWEEP | MG_FUSE_NORM_SWEEP | MG_FUSE_PAIRS | MG_FUSE_COARSE_ZERO_SWEEP | MG_FUSE_LDS_TAIL | \
+                                     MG_FUSE_SWEEP_RESTRICT | MG_FUSE_ZERO_TRIPLE | MG_FUSE_PROLONG_PAIR | MG_FUSE_TRIPLE_2D | \
+                                     MG_FUSE_PROLONG_PAIR_SLAB | MG_FUSE_CHEBY)
+/* row-dependent coefficients (-mesh 1/2; 2-D, fp64): the two passes that exist in 3-D alone and have no row-table form */
+#define MG_FUSE_NO_ROW_TABLE_FORM   (MG_FUSE_MIXED_CORRECT | MG_FUSE_RES_RESTRICT_SMALL)
 
 /* the fields of one level in one precision (index 0: fp64, 1: fp32) */
 typedef struct mg_fset {
@@ -32,6 +39,9 @@ typedef struct mg_fset {
     int bfar_ok;            /* bfar's hi ghost plane is valid (b of a level changes only when the restriction above rewrites it) */
     mgk_geom gfar;
 } mg_fset;
+
+/* u of this field set was just rewritten: its ghost planes are stale and no exchange of them is travelling */
+static inline void mgi_u_rewritten(mg_fset *F) { F->u_ghost_ok = 0; F->u_ghost_pending = 0; }
 
 typedef struct mg_level {
     int n;                  /* unknowns per side of the whole grid */

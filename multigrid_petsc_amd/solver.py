@@ -4,6 +4,7 @@ Names follow the reference driver (src/poisson.c:27-138): SetUp -> Assemble (set
 Solve -> Postprocessing (error_norms, solution).  Plumbing only; all work happens in the C library.
 """
 import ctypes as C
+import enum
 
 import numpy as np
 
@@ -21,6 +22,28 @@ class MgConfig(C.Structure):
 
 class MgError(RuntimeError):
     pass
+
+
+class Fuse(enum.IntFlag):
+    """The bits of Solver(fuse=...), mg_config.fuse: mg_fuse_bits of include/mgsolve.h, which says what each pass is.  The values are ABI
+    (plain ints are taken everywhere); value 64 is unassigned, accepted and ignored.  fuse=-1 selects DEFAULT."""
+    RESNORM = 1
+    PROLONG_SWEEP = 2
+    RES_RESTRICT = 4
+    NORM_SWEEP = 8
+    MIXED_CORRECT = 16
+    PAIRS = 32
+    RES_RESTRICT_SMALL = 128
+    COARSE_ZERO_SWEEP = 256
+    LDS_TAIL = 512
+    SWEEP_RESTRICT = 1024
+    ZERO_TRIPLE = 2048
+    PROLONG_PAIR = 4096
+    TRIPLE_2D = 8192
+    PROLONG_PAIR_SLAB = 16384
+    CHEBY = 32768
+    DEFAULT = (RESNORM | PROLONG_SWEEP | RES_RESTRICT | NORM_SWEEP | MIXED_CORRECT | PAIRS | COARSE_ZERO_SWEEP | LDS_TAIL | SWEEP_RESTRICT |
+               ZERO_TRIPLE | PROLONG_PAIR | TRIPLE_2D | PROLONG_PAIR_SLAB | CHEBY)
 
 
 _KSP = {"richardson": 0, "chebyshev": 1}

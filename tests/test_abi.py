@@ -218,3 +218,68 @@ def test_own_driver_refuses_option_combinations_it_does_not_build(tmp_path):
                       (["-pc_type", "ilu"], "only -pc_type jacobi"), (["-cycle", "3"], "only -cycle 0")):
         p = subprocess.run([exe] + args, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
         assert p.returncode == 2 and msg in p.stdout, (args, p.returncode, p.stdout)
+
+
+# mg_fuse_bits (include/mgsolve.h): the values are ABI -- tests, bench.py, the tools and `mgpoisson -mg_fuse N` pass numerals
+FUSE_BITS = {"RESNORM": 1, "PROLONG_SWEEP": 2, "RES_RESTRICT": 4, "NORM_SWEEP": 8, "MIXED_CORRECT": 16, "PAIRS": 32, "RES_RESTRICT_SMALL": 128,
+             "COARSE_ZERO_SWEEP": 256, "LDS_TAIL": 512, "SWEEP_RESTRICT": 1024, "ZERO_TRIPLE": 2048, "PROLONG_PAIR": 4096, "TRIPLE_2D": 8192,
+             "PROLONG_PAIR_SLAB": 16384, "CHEBY": 32768}
+FUSE_DEFAULT = 63 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768      # what mg_solver_create has always made of fuse = -1
+
+
+def _cc(args):
+    import shutil
+    import subprocess
+    if shutil.which(args[0]) is None:
+        pytest.skip("no host compiler")
+    p = subprocess.run(args, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert p.returncode == 0, " ".join(args) + "\n" + p.stdout[-3000:]
+
+
+def test_fuse_bit_names_of_the_header_and_of_the_python_mirror(tmp_path):
+    """every MG_FUSE_* enumerator of include/mgsolve.h, as a C compiler evaluates it, equals the member of multigrid_petsc_amd.Fuse of that
+    name; the named bits are the distinct powers of two they have always been, and MG_FUSE_DEFAULT is the mask fuse = -1 has always selected"""
+    import subprocess
+    from multigrid_petsc_amd import Fuse
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mgsolve.h")).read(), flags=re.S)
+    names = re.findall(r"\bMG_FUSE_([A-Z0-9_]+)\s*=", re.search(r"typedef enum mg_fuse_bits \{(.*?)\}", txt, flags=re.S).group(1))
+    assert len(names) == len(set(names)) and set(names) == set(FUSE_BITS) | {"DEFAULT"}
+    (tmp_path / "fuse.c").write_text('#include <stdio.h>\n#include "mgsolve.h"\nint main(void) {\n'
+                                     + "".join(f'    printf("{n} %d\\n", (int)MG_FUSE_{n});\n' for n in names) + "    return 0;\n}\n")
+    _cc(["gcc", "-std=c99", "-I" + os.path.join(ROOT, "include"), str(tmp_path / "fuse.c"), "-o", str(tmp_path / "fuse")])
+    out = subprocess.run([str(tmp_path / "fuse")], check=True, stdout=subprocess.PIPE, text=True).stdout
+    header = {l.split()[0]: int(l.split()[1]) for l in out.splitlines()}
+    assert header == {n: int(m) for n, m in Fuse.__members__.items()}
+    bits = {n: v for n, v in header.items() if n != "DEFAULT"}
+    assert bits == FUSE_BITS
+    assert all(v > 0 and v & (v - 1) == 0 for v in bits.values()) and len(set(bits.values())) == len(bits)
+    assert header["DEFAULT"] == FUSE_DEFAULT == int(Fuse.DEFAULT)
+    assert not header["DEFAULT"] & (64 | FUSE_BITS["RES_RESTRICT_SMALL"])          # (64 is unassigned, bit 7 is for tests)
+
+
+def test_fuse_default_by_name_runs_the_cycle_of_minus_one(tmp_path):
+    """the own driver over tests/mock_mgk.cpp (csrc/mg_solver.c + mg_comm.c, as tests/test_host_sanitized.py links it), 2-D npts 33, 4 levels,
+    two cycles: -mg_fuse <Fuse.DEFAULT> and -mg_fuse -1 take the same passes and leave the same residual history and the same field, digit for
+    digit (%.16e prints a double exactly)"""
+    import subprocess
+    from multigrid_petsc_amd import Fuse
+    out = os.path.join(ROOT, "tests", "_san")
+    os.makedirs(out, exist_ok=True)
+    csrc = os.path.join(ROOT, "multigrid_petsc_amd", "csrc")
+    flags = ["-O1", "-ffp-contract=off", "-D_POSIX_C_SOURCE=200809L", "-I" + os.path.join(ROOT, "include")]
+    mock = os.path.join(out, "abi_mock_mgk.o")
+    _cc(["g++", "-std=c++17"] + flags + ["-c", os.path.join(ROOT, "tests", "mock_mgk.cpp"), "-o", mock])
+    exe = os.path.join(out, "abi_mgpoisson")
+    _cc(["gcc", "-std=c99"] + flags + [os.path.join(csrc, "driver", "mgpoisson.c"), os.path.join(csrc, "mg_solver.c"), os.path.join(csrc, "mg_comm.c"), mock,
+                                      "-o", exe, "-lstdc++", "-lm", "-ldl", "-lpthread"])
+    res = {}
+    for fuse in (-1, int(Fuse.DEFAULT), 0):
+        d = tmp_path / f"fuse{fuse}"
+        d.mkdir()
+        p = subprocess.run([exe, "-dim", "2", "-npts", "33", "-levels", "4", "-iter", "2", "-ksp_richardson_scale", "0.8", "-pc_type", "jacobi", "-mg_fuse", str(fuse),
+                            "-write_fields", "1"], cwd=d, env=dict(os.environ, MOCK_MGK_STATS="1"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+        assert p.returncode == 0 and "Number of iterations:\t\t2" in p.stdout, p.stdout[-2000:]
+        res[fuse] = ((d / "rData.dat").read_text(), (d / "uData.dat").read_text(), re.findall(r"MOCK_MGK_STATS.*", p.stdout))
+    assert len(res[-1][0].split()) == 3 and len(res[-1][1].split()) == 31 * 31
+    assert res[int(Fuse.DEFAULT)] == res[-1]
+    assert res[0][1] == res[-1][1]                  # (every mask computes the same field: the bits choose passes, not arithmetic)
