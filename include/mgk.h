@@ -566,9 +566,61 @@ int  mgk_line_forward_f64(mgk_ctx *ctx, const mgk_geom *g, const double *atab, c
 int  mgk_line_backward_f64(mgk_ctx *ctx, const mgk_geom *g, const double *qtab, double scale, const double *z, const double *u,
                            double *unew, void *stream);
 
-/* tuning knobs (profiling only), per calling thread: <=0 keeps the built-in choice.  They are GLOBAL to that thread, not per kernel: the
- * marching stencil kernels read (variant, z chunk), the Krylov passes and the two line kernels read variant = 0 / 1 as their store policy,
- * and the line kernels read the second argument as their prefetch depth in rows -- set them back to (-1, -1) after measuring one kernel. */
+/* Named values of mgk_set_tuning's first argument.  From 30 up a value selects ONE form of ONE launcher (every other launcher takes it as
+ * "no special form"); the values below 30 are read three ways, see the table under the enum.  MGK_TUNE_STORE_* name the 0 / 1 reading of
+ * the Krylov and line passes.  mgk_set_tuning takes any int: a value nothing reads selects nothing. */
+enum mgk_tune {
+    MGK_TUNE_DEFAULT           = -1,   /* every launcher makes its built-in choice */
+    MGK_TUNE_STORE_PLAIN       = 0,    /* Krylov passes (mgk_krylov.hip), line kernels (mgk_line.hip): ordinary stores whatever the field size */
+    MGK_TUNE_STORE_NT          = 1,    /* the same passes: non-temporal stores whatever the field size */
+    MGK_TUNE_LDS_TILE          = 30,   /* residual_restrict / prolong_jacobi (3-D): the LDS-tile kernels (k_resrestrict, k_stencil) on row shapes too;
+                                          prolong_jacobi in 2-D: the LDS-tile kernel from 2047^2 on as well */
+    MGK_TUNE_ROW               = 31,   /* residual_restrict / prolong_jacobi: the register / shuffle row kernels (k_rrrow, k_pjrow), predicated loads,
+                                          ds_bpermute lane shifts */
+    MGK_TUNE_ROW_PD2           = 32,   /* once prefetch distance 2 of the row kernels; the same forms as MGK_TUNE_ROW now */
+    MGK_TUNE_ROW_UNCOND        = 33,   /* prolong_jacobi: k_pjrow with unconditional loads; residual_restrict: as MGK_TUNE_ROW */
+    MGK_TUNE_ROW_DPP           = 34,   /* the row kernels' default form (unconditional loads where built, DPP lane shifts); ALSO forces the row form
+                                          k_jrow of the plain sweeps (mgk_jacobi_*, mgk_jacobi_sumsq_*) on every full-row shape from nx = 127 */
+    MGK_TUNE_ROW_PRED_DPP      = 35,   /* prolong_jacobi: k_pjrow with predicated loads and DPP lane shifts; residual_restrict: as MGK_TUNE_ROW_DPP */
+    MGK_TUNE_J2_REG_PRED       = 36,   /* jacobi2: the register form k_jacobi2r with predicated loads / ds_bpermute on full-row shapes too; the
+                                          zero-guess form is then not offered (mgk_jacobi2_zero_ok_*) */
+    MGK_TUNE_J2_RING_PRED      = 37,   /* jacobi2: the LDS-ring form k_jacobi2 with predicated loads on full-row shapes too; no zero-guess form */
+    MGK_TUNE_PJ2D_WAVES        = 38,   /* prolong_jacobi (2-D, whole grid, constants or row tables): independent waves (k_pj2d) from nx = 3 on */
+    MGK_TUNE_J2_RING_OLD       = 39,   /* jacobi2, ring form: k_jacobi2 (the form before the instruction diet) instead of k_jacobi2b, from the zero
+                                          guess as well */
+    MGK_TUNE_SRR_TY2           = 40,   /* sweep_residual_restrict (whole grid): tiles of 2 rows (k_srr) */
+    MGK_TUNE_SRR_TY4           = 41,   /* sweep_residual_restrict (whole grid): tiles of 4 rows, swept planes in LDS (k_srr4b) */
+    MGK_TUNE_J2_ZERO_RINGB     = 45,   /* jacobi2 from the zero guess, fp64: k_jacobi2b, which fp64 leaves to fp32 by default */
+    MGK_TUNE_PJ2_COPY          = 46,   /* prolong_jacobi2 (whole grid): the copying form k_pj2r instead of the unrolled k_pj2r3 */
+    MGK_TUNE_J3_2D_MARCH       = 50,   /* jacobi3_2d (mgk_kernels3.hip): the marching form on every size */
+    MGK_TUNE_J3_2D_CHUNK4      = 51,   /* jacobi3_2d: the short-chunk form, 4 rows */
+    MGK_TUNE_J3_2D_CHUNK8      = 52,   /* jacobi3_2d: the short-chunk form, 8 rows */
+    MGK_TUNE_DISPATCH_ORDER    = 53,   /* jacobi3_2d, jacobi3_3d: wave tiles in dispatch order */
+    MGK_TUNE_XCD_ORDER         = 54,   /* jacobi3_2d: XCD-aware tile order whatever the size */
+    MGK_TUNE_RR2D_MARCH        = 55,   /* residual_restrict_2d: the marching form k_rr2d<2> */
+    MGK_TUNE_RR2D_SHORT        = 56,   /* residual_restrict_2d: chunks of two coarse rows, k_rr2d<5> */
+    MGK_TUNE_RESERVED_57       = 57,   /* nothing reads it (tests pass it as a value without a form) */
+    MGK_TUNE_J3_2D_ODD_DOWN    = 58,   /* jacobi3_2d, marching form: odd chunks march downwards */
+    MGK_TUNE_J3_2D_ALL_DOWN    = 59,   /* jacobi3_2d, marching form: every chunk marches downwards */
+    MGK_TUNE_J3_2D_STORE_PLAIN = 60,   /* jacobi3_2d: ordinary stores whatever the field size */
+    MGK_TUNE_J3_2D_STORE_NT    = 61,   /* jacobi3_2d: non-temporal stores whatever the field size */
+    MGK_TUNE_J3_3D_TY2         = 62,   /* jacobi3_3d: wave tiles of 2 rows */
+    MGK_TUNE_J3_3D_TY3         = 63,   /* jacobi3_3d: wave tiles of 3 rows (what the norm form always takes) */
+    MGK_TUNE_J3_3D_ROWWISE     = 64    /* jacobi3_3d: the sweeps row by row instead of term by term over the rows */
+};
+
+/* tuning knobs (profiling only), per calling thread: <=0 keeps the built-in choice.  They are GLOBAL to that thread, not per kernel -- set
+ * them back to (-1, -1) after measuring one kernel.  The second argument, > 0, is the length of a chunk of the marching axis (planes, rows
+ * or coarse rows) for every launcher that cuts one, and the depth of the line kernels' prefetch ring in rows.  The first argument is an
+ * enum mgk_tune or, below 30, a plain integer that three kinds of launcher read in their own way:
+ *
+ *   reader                                               0 .. 13                                        what else
+ *   k_stencil launchers (sweep, residual, apply, ...)    index into the tile table of dispatch_st:      an index the table lacks is
+ *                                                        fp64 3-D 0 1 2 3 6 9 12 13, fp64 2-D 0 1 2,     MGK_EINVAL; from 30 up: built-in
+ *                                                        fp32 0 1 2 3 (a table per format, see there)
+ *   Krylov passes, line kernels                          0 ordinary / 1 non-temporal stores              anything else: by field size
+ *   jacobi2 (mgk_jacobi2_*)                              1 the LDS-ring form / 2 the register form       anything else: by row width
+ */
 void mgk_set_tuning(int variant, int zchunk);
 
 #ifdef __cplusplus

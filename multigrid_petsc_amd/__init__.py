@@ -14,3 +14,4 @@ built libraries or without a HIP device raises.
 """
 from ._lib import load_mgk, load_mgpetsc, LibraryMissing  # noqa: F401
 from .solver import Fuse  # noqa: F401
+from .mgk import Tune, tuning  # noqa: F401

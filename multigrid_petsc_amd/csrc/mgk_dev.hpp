@@ -32,10 +32,13 @@ static inline hipStream_t S(mgk_ctx *c, void *s) { return s ? (hipStream_t)s : c
 typedef double __attribute__((address_space(4))) CDBL4;
 // per THREAD tuning knobs (mgk_set_tuning) and the fixed-order finish of per-block / per-wave partial sums (mgk_kernels.hip)
 extern thread_local int g_variant, g_zchunk;
+// the store policy the Krylov and line passes read from the knob: 0 ordinary, 1 non-temporal, -1 by field size
+static inline int store_policy() { return g_variant == MGK_TUNE_STORE_PLAIN ? 0 : g_variant == MGK_TUNE_STORE_NT ? 1 : -1; }
 int finish_to_host(mgk_ctx *c, int nparts, int nslots, hipStream_t s, double *host_out);
 int mgk_preload_kernels3();      // forces the code object of mgk_kernels3.hip to load (mgk_ctx_create)
 int mgk_preload_krylov();        // ... and that of mgk_krylov.hip
 int mgk_preload_line();          // ... and that of mgk_line.hip
+#include "mgk_launch.hpp"        // the launch rules of the host side (they read the context and the knobs above)
 #define MGK_RESULT_SLOTS 64      // >= MGK_KRYLOV_MAX + 1: the dots of an Arnoldi step and the norm that follows them
 
 // ------------------------------------------------------------------------------------------

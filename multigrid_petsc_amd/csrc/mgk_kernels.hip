@@ -790,6 +790,8 @@ static int launch_st(mgk_ctx *c, StArgs<T> &a, int nrows, hipStream_t s, int *nb
     long tiles = (long)a.ntx * a.nty;
     if (a.zend <= a.zbeg) { a.zbeg = 0; a.zend = a.nm; }
     const int nmr = a.zend - a.zbeg;      // planes marched by this launch
+    // (open-coded, not cut_chunks: the chunk count depends on the mode and the block size, chunk_planes CAPS the length here instead of
+    // raising the count, and the reducing modes refit the chunks to the partial buffer)
     int zc = g_zchunk;
     if (zc <= 0) {
         // Few, long streams: ~256-512 blocks, each marching a long run of planes over a full-row tile,
@@ -834,7 +836,7 @@ static int dispatch_st(mgk_ctx *c, const mgk_geom *g, StArgs<double> &a, hipStre
     a.nx = g->nx;
     if (g->dim == 3) {
         a.ny = g->ny; a.nm = g->nz; a.rs = g->pitch; a.ms = g->plane;
-        int v = g_variant >= 30 ? -1 : g_variant;
+        int v = g_variant >= MGK_TUNE_LDS_TILE ? -1 : g_variant;      // (the named values select no tile)
         if (v < 0) v = (MODE == MODE_RESNORM && g->nx >= 255) ? 3
                      : (g->nx >= 1023) ? ((MODE == MODE_PJACOBI || MODE == MODE_CRES32 || MODE == MODE_CHEBY) ? 9 : 12)   // on-the-fly corrections and the Chebyshev step's third operand: 512-thread blocks (a 1024-thread block is capped at 128 VGPRs and spills: Chebyshev step 9.88 -> 5.96 ms)
                      : (g->nx >= 511) ? (MODE == MODE_PJACOBI ? 13 : 6)             // fused prolongation at 511^3: 0.91 -> 0.73 ms
@@ -852,7 +854,7 @@ static int dispatch_st(mgk_ctx *c, const mgk_geom *g, StArgs<double> &a, hipStre
         }
     } else {
         a.ny = 1; a.nm = g->ny; a.rs = 0; a.ms = g->pitch;
-        int v = g_variant >= 30 ? -1 : g_variant;
+        int v = g_variant >= MGK_TUNE_LDS_TILE ? -1 : g_variant;      // (the named values select no tile)
         if (v < 0) v = (g->nx >= 511) ? 2 : (g->nx >= 255 ? 1 : 0);
         switch (v) {
             case 0: return launch_st<double, 2, 1, 1, 1, MODE>(c, a, 1, s, nblocks);
@@ -868,7 +870,7 @@ static int dispatch_st(mgk_ctx *c, const mgk_geom *g, StArgs<float> &a, hipStrea
     a.nx = g->nx;
     if (g->dim != 3) return fail(MGK_EINVAL, "fp32 stencil kernels are built for 3-D only");
     a.ny = g->ny; a.nm = g->nz; a.rs = g->pitch; a.ms = g->plane;
-    int v = g_variant >= 30 ? -1 : g_variant;
+    int v = g_variant >= MGK_TUNE_LDS_TILE ? -1 : g_variant;      // (the named values select no tile)
     if (v < 0) v = (g->nx >= 1023) ? (MODE == MODE_PJACOBI ? 3 : 2) : (g->nx >= 511) ? 1 : 0;
     switch (v) {
         case 0: return launch_st<float, 3, 1, 2, 2, MODE>(c, a, g->ny, s, nblocks);   // 256 x 4, 128 thr
@@ -881,11 +883,8 @@ static int dispatch_st(mgk_ctx *c, const mgk_geom *g, StArgs<float> &a, hipStrea
 
 template <typename T>
 static void set_coef(StArgs<T> &a, const mgk_geom *g, const double *coef) {
-    if (g->dim == 3) {
-        a.a0 = (T)coef[0]; a.a1 = (T)coef[1]; a.a2 = (T)coef[2]; a.a3 = (T)coef[3]; a.a4 = (T)coef[4]; a.a5 = (T)coef[5]; a.a6 = (T)coef[6];
-    } else {
-        a.a0 = (T)coef[0]; a.a1 = (T)0; a.a2 = (T)coef[1]; a.a3 = (T)coef[2]; a.a4 = (T)coef[3]; a.a5 = (T)0; a.a6 = (T)coef[4];
-    }
+    if (g->dim == 3) set_coef7(a, coef);
+    else { a.a1 = (T)0; a.a5 = (T)0; set_coef5(a, coef); }
 }
 
 // register / shuffle form of the plain sweeps (k_jrow, defined with the other row kernels further down)
@@ -893,17 +892,36 @@ template <typename T> static bool jrow_ok(const mgk_geom *g);
 template <typename T, bool NORM>
 static int launch_jrow(mgk_ctx *c, const mgk_geom *g, const StArgs<T> &a, int zbeg, int zend, hipStream_t s, double *partials, int max_partials, int *nparts);
 
+// one sweep / the residual on the marching planes [zbeg, zend); `bad` / `range`: the entry point's messages (fp32: 3-D only, dispatch_st says so)
+template <typename T>
+static int jacobi_range(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale, const T *b, const T *u, T *unew,
+                        int zbeg, int zend, void *stream, const char *bad, const char *range) {
+    if (!c || !g || !coef || !b || !u || !unew || u == unew) return fail(MGK_EINVAL, bad);
+    const int nm = (sizeof(T) == 8 && g->dim != 3) ? g->ny : g->nz;
+    if (zbeg < 0 || zend > nm || zbeg >= zend) return fail(MGK_EINVAL, range);
+    StArgs<T> a; memset(&a, 0, sizeof(a));
+    a.u = u + g->org; a.b = b + g->org; a.out = unew + g->org;
+    set_coef(a, g, coef); a.dinv = (T)dinv; a.scale = (T)scale;
+    a.zbeg = zbeg; a.zend = zend;
+    if (jrow_ok<T>(g)) return launch_jrow<T, false>(c, g, a, zbeg, zend, S(c, stream), nullptr, 0, nullptr);
+    return dispatch_st<MODE_JACOBI>(c, g, a, S(c, stream), nullptr);
+}
+template <typename T>
+static int residual_range(mgk_ctx *c, const mgk_geom *g, const double *coef, const T *b, const T *u, T *r, int zbeg, int zend, void *stream,
+                          const char *bad, const char *range) {
+    if (!c || !g || !coef || !b || !u || !r || u == r) return fail(MGK_EINVAL, bad);
+    const int nm = (sizeof(T) == 8 && g->dim != 3) ? g->ny : g->nz;
+    if (zbeg < 0 || zend > nm || zbeg >= zend) return fail(MGK_EINVAL, range);
+    StArgs<T> a; memset(&a, 0, sizeof(a));
+    a.u = u + g->org; a.b = b + g->org; a.out = r + g->org;
+    set_coef(a, g, coef);
+    a.zbeg = zbeg; a.zend = zend;
+    return dispatch_st<MODE_RESIDUAL>(c, g, a, S(c, stream), nullptr);
+}
 extern "C" int mgk_jacobi_range_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                                     const double *b, const double *u, double *unew, int zbeg, int zend, void *stream) {
-    if (!c || !g || !coef || !b || !u || !unew || u == unew) return fail(MGK_EINVAL, "mgk_jacobi_f64: bad arguments");
-    const int nm = (g->dim == 3) ? g->nz : g->ny;
-    if (zbeg < 0 || zend > nm || zbeg >= zend) return fail(MGK_EINVAL, "mgk_jacobi_range_f64: empty or out-of-range plane range");
-    StArgs<double> a; memset(&a, 0, sizeof(a));
-    a.u = u + g->org; a.b = b + g->org; a.out = unew + g->org;
-    set_coef(a, g, coef); a.dinv = dinv; a.scale = scale;
-    a.zbeg = zbeg; a.zend = zend;
-    if (jrow_ok<double>(g)) return launch_jrow<double, false>(c, g, a, zbeg, zend, S(c, stream), nullptr, 0, nullptr);
-    return dispatch_st<MODE_JACOBI>(c, g, a, S(c, stream), nullptr);
+    return jacobi_range<double>(c, g, coef, dinv, scale, b, u, unew, zbeg, zend, stream, "mgk_jacobi_f64: bad arguments",
+                                "mgk_jacobi_range_f64: empty or out-of-range plane range");
 }
 extern "C" int mgk_jacobi_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                               const double *b, const double *u, double *unew, void *stream) {
@@ -924,14 +942,8 @@ extern "C" int mgk_cheby_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, 
 
 extern "C" int mgk_residual_range_f64(mgk_ctx *c, const mgk_geom *g, const double *coef,
                                       const double *b, const double *u, double *r, int zbeg, int zend, void *stream) {
-    if (!c || !g || !coef || !b || !u || !r || u == r) return fail(MGK_EINVAL, "mgk_residual_f64: bad arguments");
-    const int nm = (g->dim == 3) ? g->nz : g->ny;
-    if (zbeg < 0 || zend > nm || zbeg >= zend) return fail(MGK_EINVAL, "mgk_residual_range_f64: empty or out-of-range plane range");
-    StArgs<double> a; memset(&a, 0, sizeof(a));
-    a.u = u + g->org; a.b = b + g->org; a.out = r + g->org;
-    set_coef(a, g, coef);
-    a.zbeg = zbeg; a.zend = zend;
-    return dispatch_st<MODE_RESIDUAL>(c, g, a, S(c, stream), nullptr);
+    return residual_range<double>(c, g, coef, b, u, r, zbeg, zend, stream, "mgk_residual_f64: bad arguments",
+                                  "mgk_residual_range_f64: empty or out-of-range plane range");
 }
 extern "C" int mgk_residual_f64(mgk_ctx *c, const mgk_geom *g, const double *coef,
                                 const double *b, const double *u, double *r, void *stream) {
@@ -2100,34 +2112,34 @@ extern "C" int mgk_prolong_jacobi2_ok_f64(const mgk_geom *gf, const mgk_geom *gc
     const int w = (gf->nx + 1) / 128;
     return (w == 4 || w == 8) ? 1 : 0;                                         // rows of 512 / 1024 (n = 511, 1023)
 }
+// the arguments and the z chunks of both forms (whole grid: planes [0, nz), no chunk_planes hint; slab: [zbeg, zend)); returns the block count
+static unsigned pj2_fill(PJ2Args &a, mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
+                         const double *b, const double *uc, const double *u, double *unew, int nzr, bool slab) {
+    memset(&a, 0, sizeof(a));
+    a.u = u ? u + gf->org : nullptr; a.b = b + gf->org; a.uc = uc + gc->org; a.out = unew + gf->org;
+    a.nx = gf->nx; a.ny = gf->ny; a.nz = gf->nz; a.nxc = gc->nx; a.nyc = gc->ny; a.nzc = gc->nz;
+    a.rs = gf->pitch; a.ms = gf->plane; a.crs = gc->pitch; a.cms = gc->plane;
+    set_coef7(a, coef);
+    a.dinv = dinv; a.scale = scale;
+    a.nty = (gf->ny + 3) / 4;
+    const long target = ((gf->nx + 1) / 128 > 4) ? 256 : 512;    // 512-thread blocks: one per CU; 256-thread blocks: two
+    // even: every chunk starts on an even plane; not clamped to the extent (the kernel stops at the last plane)
+    const Chunks ch = cut_chunks(c, nzr, a.nty, target, {/*min*/ 8, false, /*even*/ true, /*clamp*/ false, /*hint*/ 1, slab ? 1 : 0});
+    a.zc = ch.len;
+    return (unsigned)(a.nty * ch.count);
+}
 // unew = J(J(u + P uc)) (ZU: J(J(0 + P uc)), u not read): one launch of the whole-grid form
 template <bool ZU>
 static int prolong_jacobi2(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
                            const double *b, const double *uc, const double *u, double *unew, void *stream) {
-    PJ2Args a; memset(&a, 0, sizeof(a));
-    a.u = ZU ? nullptr : u + gf->org; a.b = b + gf->org; a.uc = uc + gc->org; a.out = unew + gf->org;
-    a.nx = gf->nx; a.ny = gf->ny; a.nz = gf->nz; a.nxc = gc->nx; a.nyc = gc->ny; a.nzc = gc->nz;
-    a.rs = gf->pitch; a.ms = gf->plane; a.crs = gc->pitch; a.cms = gc->plane;
-    a.a0 = coef[0]; a.a1 = coef[1]; a.a2 = coef[2]; a.a3 = coef[3]; a.a4 = coef[4]; a.a5 = coef[5]; a.a6 = coef[6];
-    a.dinv = dinv; a.scale = scale;
-    a.nty = (gf->ny + 3) / 4;
-    const long target = ((gf->nx + 1) / 128 > 4) ? 256 : 512;    // 512-thread blocks: one per CU; 256-thread blocks: two
-    long nch = (a.nty >= target) ? 1 : (target + a.nty - 1) / a.nty;
-    if (g_zchunk > 0) nch = (gf->nz + g_zchunk - 1) / g_zchunk;
-    int zc = (int)((gf->nz + nch - 1) / nch);
-    zc = (zc + 1) & ~1;                                          // even: every chunk starts on an even plane
-    if (zc < 8) zc = 8;
-    a.zc = zc;
-    const unsigned nblk = (unsigned)(a.nty * ((gf->nz + zc - 1) / zc));
-    if (ZU) {                                                    // (the unrolled form only)
-        if ((gf->nx + 1) / 128 == 4) hipLaunchKernelGGL((k_pj2r3<4, false, true>), dim3(nblk), dim3(256), 0, S(c, stream), a);
-        else hipLaunchKernelGGL((k_pj2r3<8, false, true>), dim3(nblk), dim3(512), 0, S(c, stream), a);
-    } else if ((gf->nx + 1) / 128 == 4 && g_variant != 46) hipLaunchKernelGGL((k_pj2r3<4, false>), dim3(nblk), dim3(256), 0, S(c, stream), a);   // round 3: the unrolled form on rows of
-                                                                                                        // 512 too: 511^3 0.651 -> 0.601 ms (253 VGPRs, two blocks per CU)
-    else if ((gf->nx + 1) / 128 == 4) hipLaunchKernelGGL((k_pj2r<4>), dim3(nblk), dim3(256), 0, S(c, stream), a);
-    else if (g_variant != 46) hipLaunchKernelGGL((k_pj2r3<8, false>), dim3(nblk), dim3(512), 0, S(c, stream), a);      // marching loop unrolled by three, the plane roles
-                                                                                                        // permuted instead of copied: 4.80 against 4.90 ms (46: the copying form)
-    else hipLaunchKernelGGL((k_pj2r<8>), dim3(nblk), dim3(512), 0, S(c, stream), a);
+    PJ2Args a;
+    const unsigned nblk = pj2_fill(a, c, gf, gc, coef, dinv, scale, b, uc, ZU ? nullptr : u, unew, gf->nz, false);
+    const int w = (gf->nx + 1) / 128;
+    // the marching loop unrolled by three, the plane roles permuted instead of copied: 1023^3 4.80 against 4.90 ms, 511^3 0.651 -> 0.601 ms
+    // (253 VGPRs, two blocks per CU); MGK_TUNE_PJ2_COPY: the copying form k_pj2r (not built from the zero guess)
+    if (ZU) LAUNCH_WX(width_48, w, (k_pj2r3<WX, false, true>), nblk, S(c, stream), a);
+    else if (g_variant != MGK_TUNE_PJ2_COPY) LAUNCH_WX(width_48, w, (k_pj2r3<WX, false>), nblk, S(c, stream), a);
+    else LAUNCH_WX(width_48, w, (k_pj2r<WX>), nblk, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2163,41 +2175,23 @@ extern "C" int mgk_prolong_jacobi2_slab_f64(mgk_ctx *c, const mgk_geom *gf, cons
                                             const double *far, const double *cfar, int has_lo, int has_hi, int zbeg, int zend, void *stream) {
     if (!c || !coef || !b || !uc || !u || !unew || u == unew || !mgk_prolong_jacobi2_slab_ok_f64(gf, gc, has_hi))
         return fail(MGK_EINVAL, "mgk_prolong_jacobi2_slab_f64: bad arguments / shape not built");
-    if ((has_lo || has_hi) && (!far || !gfar || gfar->dim != 3 || gfar->nz != 2 || gfar->nx != gf->nx || gfar->ny != gf->ny || gfar->pitch != gf->pitch))
+    if ((has_lo || has_hi) && !far_geom_ok(gfar, far, gf))
         return fail(MGK_EINVAL, "mgk_prolong_jacobi2_slab_f64: the far-plane field must have the geometry (nx, ny, 2) of the slab");
-    if (has_lo && (!cfar || !gcfar || gcfar->dim != 3 || gcfar->nz != 2 || gcfar->nx != gc->nx || gcfar->ny != gc->ny || gcfar->pitch != gc->pitch))
+    if (has_lo && !far_geom_ok(gcfar, cfar, gc))
         return fail(MGK_EINVAL, "mgk_prolong_jacobi2_slab_f64: the coarse far-plane field must have the geometry (nxc, nyc, 2) of the coarse slab");
     if (zbeg < 0 || (zbeg & 1) || zend > gf->nz || zbeg >= zend) return fail(MGK_EINVAL, "mgk_prolong_jacobi2_slab_f64: empty, odd or out-of-range plane range");
-    PJ2Args a; memset(&a, 0, sizeof(a));
-    a.u = u + gf->org; a.b = b + gf->org; a.uc = uc + gc->org; a.out = unew + gf->org;
-    a.nx = gf->nx; a.ny = gf->ny; a.nz = gf->nz; a.nxc = gc->nx; a.nyc = gc->ny; a.nzc = gc->nz;
-    a.rs = gf->pitch; a.ms = gf->plane; a.crs = gc->pitch; a.cms = gc->plane;
-    a.a0 = coef[0]; a.a1 = coef[1]; a.a2 = coef[2]; a.a3 = coef[3]; a.a4 = coef[4]; a.a5 = coef[5]; a.a6 = coef[6];
-    a.dinv = dinv; a.scale = scale;
+    PJ2Args a;
+    const unsigned nblk = pj2_fill(a, c, gf, gc, coef, dinv, scale, b, uc, u, unew, zend - zbeg, true);
     a.has_lo = has_lo ? 1 : 0; a.has_hi = has_hi ? 1 : 0;
-    a.far_lo = has_lo ? far + gfar->org - gfar->plane : nullptr;
-    a.far_hi = has_hi ? far + gfar->org + 2 * gfar->plane : nullptr;
-    a.cfar_lo = has_lo ? cfar + gcfar->org - gcfar->plane : nullptr;
+    a.far_lo = far_lo_plane(far, gfar, has_lo);
+    a.far_hi = far_hi_plane(far, gfar, has_hi);
+    a.cfar_lo = far_lo_plane(cfar, gcfar, has_lo);
     a.zbeg = zbeg; a.zend = zend;
-    const int nzr = zend - zbeg;
-    a.nty = (gf->ny + 3) / 4;
-    const long target = ((gf->nx + 1) / 128 > 4) ? 256 : 512;
-    long nch = (a.nty >= target) ? 1 : (target + a.nty - 1) / a.nty;
-    if (g_zchunk > 0) nch = (nzr + g_zchunk - 1) / g_zchunk;
-    else if (c->chunk_planes > 0 && nch < (nzr + c->chunk_planes - 1) / c->chunk_planes) nch = (nzr + c->chunk_planes - 1) / c->chunk_planes;
-    int zc = (int)((nzr + nch - 1) / nch);
-    zc = (zc + 1) & ~1;                                          // even: every chunk starts on an even plane
-    if (zc < 8) zc = 8;
-    a.zc = zc;
-    const unsigned nblk = (unsigned)(a.nty * ((nzr + zc - 1) / zc));
-    if ((gf->nx + 1) / 128 == 4) hipLaunchKernelGGL((k_pj2r3<4, true>), dim3(nblk), dim3(256), 0, S(c, stream), a);
-    else hipLaunchKernelGGL((k_pj2r3<8, true>), dim3(nblk), dim3(512), 0, S(c, stream), a);
+    LAUNCH_WX(width_48, (gf->nx + 1) / 128, (k_pj2r3<WX, true>), nblk, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-template <typename T> struct j2norm { static constexpr bool built = false; };
-template <> struct j2norm<double> { static constexpr bool built = true; };
 template <typename T>
 static int jacobi2(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                    const T *b, const T *u, T *unew, const T *far_lo, const T *far_hi, int zbeg, int zend, void *stream,
@@ -2209,7 +2203,7 @@ static int jacobi2(mgk_ctx *c, const mgk_geom *g, const double *coef, double din
     J2Args<T> a; memset(&a, 0, sizeof(a));
     a.u = u + g->org; a.b = b + g->org; a.out = unew + g->org;
     a.nx = g->nx; a.ny = g->ny; a.nz = g->nz; a.rs = g->pitch; a.ms = g->plane;
-    a.a0 = (T)coef[0]; a.a1 = (T)coef[1]; a.a2 = (T)coef[2]; a.a3 = (T)coef[3]; a.a4 = (T)coef[4]; a.a5 = (T)coef[5]; a.a6 = (T)coef[6];
+    set_coef7(a, coef);
     a.dinv = (T)dinv; a.scale = (T)scale;
     a.far_lo = far_lo; a.far_hi = far_hi; a.has_lo = far_lo != nullptr; a.has_hi = far_hi != nullptr;
     if (zbeg < 0 || zend > g->nz || zbeg >= zend) return fail(MGK_EINVAL, "mgk_jacobi2: empty or out-of-range plane range");
@@ -2223,32 +2217,19 @@ static int jacobi2(mgk_ctx *c, const mgk_geom *g, const double *coef, double din
     // rows of <= 2 waves (255^3, the third level of the headline): blocks of 128 threads, a chunk per SIMD is too few waves to
     // cover the latency -- 1024 blocks of 16 planes (in the 511^3 cycle: 118 -> 88 us, zero-guess form 126 -> 81; 8 planes 104 / 89)
     const long target = (w > 4) ? 256 : ((sizeof(T) == 4 || w <= 2) ? 1024 : 512);      // fp32 1023^3: 1024 blocks 2.72 ms, 512 blocks 2.84 ms
-    long nch = (a.nty >= target) ? 1 : (target + a.nty - 1) / a.nty;
-    if (g_zchunk > 0) nch = (nzr + g_zchunk - 1) / g_zchunk;
-    else if (c->chunk_planes > 0 && nch < (nzr + c->chunk_planes - 1) / c->chunk_planes) nch = (nzr + c->chunk_planes - 1) / c->chunk_planes;
-    int zc = (int)((nzr + nch - 1) / nch);
-    if (zc < 8) zc = 8;
-    if (zc > nzr) zc = nzr;
-    a.zc = zc;
-    const long ntz = (nzr + zc - 1) / zc;
-    const unsigned nblk = (unsigned)(a.nty * ntz);
+    const Chunks ch = cut_chunks(c, nzr, a.nty, target, {/*min*/ 8, false, /*even*/ false, /*clamp*/ true, /*hint*/ 1, 1});
+    a.zc = ch.len;
+    const unsigned nblk = (unsigned)(a.nty * ch.count);
     hipStream_t s = S(c, stream);
     if (norm_parts) {
         // with the residual norm of the input field: the register form on full-row shapes only
         constexpr int WRn = 64 * VX;
-        if (!j2norm<T>::built || (g->nx + 1) % WRn != 0 || (g->ny + 1) % 4 != 0 || part_off < 0 || (long)nblk > c->max_partials - part_off)
+        if (sizeof(T) != 8 || (g->nx + 1) % WRn != 0 || (g->ny + 1) % 4 != 0 || part_off < 0 || (long)nblk > c->max_partials - part_off)
             return fail(MGK_EINVAL, "mgk_jacobi2_sumsq: built for fp64 full-row shapes (n = 127, 255, 511, 1023)");
         a.partials = c->partials + part_off;
-        if constexpr (j2norm<T>::built) {
-            if (norm_mode == 2) {
-                if (w <= 1) hipLaunchKernelGGL((k_jacobi2r<T, 1, 3, 2>), dim3(nblk), dim3(64), 0, s, a);
-                else if (w <= 2) hipLaunchKernelGGL((k_jacobi2r<T, 2, 3, 2>), dim3(nblk), dim3(128), 0, s, a);
-                else if (w <= 4) hipLaunchKernelGGL((k_jacobi2r<T, 4, 3, 2>), dim3(nblk), dim3(256), 0, s, a);
-                else hipLaunchKernelGGL((k_jacobi2r<T, 8, 3, 2>), dim3(nblk), dim3(512), 0, s, a);
-            } else if (w <= 1) hipLaunchKernelGGL((k_jacobi2r<T, 1, 3, 1>), dim3(nblk), dim3(64), 0, s, a);
-            else if (w <= 2) hipLaunchKernelGGL((k_jacobi2r<T, 2, 3, 1>), dim3(nblk), dim3(128), 0, s, a);
-            else if (w <= 4) hipLaunchKernelGGL((k_jacobi2r<T, 4, 3, 1>), dim3(nblk), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_jacobi2r<T, 8, 3, 1>), dim3(nblk), dim3(512), 0, s, a);
+        if constexpr (sizeof(T) == 8) {                                 // (the norm forms are built for fp64 only)
+            if (norm_mode == 2) LAUNCH_WX(width_1248, w, (k_jacobi2r<T, WX, 3, 2>), nblk, s, a);
+            else LAUNCH_WX(width_1248, w, (k_jacobi2r<T, WX, 3, 1>), nblk, s, a);
         }
         HIPCHK(hipGetLastError());
         *norm_parts = (int)nblk;
@@ -2257,53 +2238,32 @@ static int jacobi2(mgk_ctx *c, const mgk_geom *g, const double *coef, double din
     // one 512-thread block per CU (fp64, 1023^3): the one-barrier variant (4.51 vs 5.15 ms per pass); smaller blocks run two
     // per CU and hide the second barrier, and prefer the ring variant's full-step prefetch distance (fp64 511^3: 0.66 vs
     // 0.72 ms; fp32 1023^3: 3.98 vs 7.29 ms, the register variant is at the 256-VGPR limit there)
-    const bool ring = (g_variant == 1) || (g_variant == 37) || (g_variant != 2 && g_variant != 36 && !(sizeof(T) == 8 && w > 4));
-    // full-row shapes: unconditional loads + DPP lane shifts (tuning variants 36 / 37 keep the predicated / ds_bpermute form)
+    const bool ring = (g_variant == 1) || (g_variant == MGK_TUNE_J2_RING_PRED) || (g_variant != 2 && g_variant != MGK_TUNE_J2_REG_PRED && !(sizeof(T) == 8 && w > 4));
+    // full-row shapes: unconditional loads + DPP lane shifts (MGK_TUNE_J2_REG_PRED / _RING_PRED keep the predicated / ds_bpermute form)
     constexpr int WR = 64 * VX;
-    const bool full = (g->nx + 1) % WR == 0 && (g->ny + 1) % 4 == 0 && g_variant != 36 && g_variant != 37;
+    const bool full = (g->nx + 1) % WR == 0 && (g->ny + 1) % 4 == 0 && g_variant != MGK_TUNE_J2_REG_PRED && g_variant != MGK_TUNE_J2_RING_PRED;
     if (zero_guess) {
         if (!full || far_lo || far_hi || norm_parts) return fail(MGK_EINVAL, "mgk_jacobi2_zero: built for whole grids of full-row shape (the LDS-ring form of the two-sweep kernel)");
-        if (g_variant == 39 || (sizeof(T) == 8 && g_variant != 45)) {   // the form before the instruction diet: 39 forces it; fp64 keeps it
-                                                                        // (511^3: 0.471 against 0.488 ms; 45 forces the new form)
-            if (w <= 1) hipLaunchKernelGGL((k_jacobi2<T, 1, 3, true>), dim3(nblk), dim3(64), 0, s, a);
-            else if (w <= 2) hipLaunchKernelGGL((k_jacobi2<T, 2, 3, true>), dim3(nblk), dim3(128), 0, s, a);
-            else if (w <= 4) hipLaunchKernelGGL((k_jacobi2<T, 4, 3, true>), dim3(nblk), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_jacobi2<T, 8, 3, true>), dim3(nblk), dim3(512), 0, s, a);
-        } else if (w <= 1) hipLaunchKernelGGL((k_jacobi2b<T, 1, true>), dim3(nblk), dim3(64), 0, s, a);
-        else if (w <= 2) hipLaunchKernelGGL((k_jacobi2b<T, 2, true>), dim3(nblk), dim3(128), 0, s, a);
-        else if (w <= 4) hipLaunchKernelGGL((k_jacobi2b<T, 4, true>), dim3(nblk), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_jacobi2b<T, 8, true>), dim3(nblk), dim3(512), 0, s, a);
+        if (g_variant == MGK_TUNE_J2_RING_OLD || (sizeof(T) == 8 && g_variant != MGK_TUNE_J2_ZERO_RINGB)) {   // the form before the instruction diet; fp64 keeps it
+                                                                        // (511^3: 0.471 against 0.488 ms; MGK_TUNE_J2_ZERO_RINGB forces the new form)
+            LAUNCH_WX(width_1248, w, (k_jacobi2<T, WX, 3, true>), nblk, s, a);
+        } else LAUNCH_WX(width_1248, w, (k_jacobi2b<T, WX, true>), nblk, s, a);
         HIPCHK(hipGetLastError());
         return 0;
     }
     if (ring) {
-        if (full && g_variant != 39) {
-            if (w <= 1) hipLaunchKernelGGL((k_jacobi2b<T, 1, false>), dim3(nblk), dim3(64), 0, s, a);
-            else if (w <= 2) hipLaunchKernelGGL((k_jacobi2b<T, 2, false>), dim3(nblk), dim3(128), 0, s, a);
-            else if (w <= 4) hipLaunchKernelGGL((k_jacobi2b<T, 4, false>), dim3(nblk), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_jacobi2b<T, 8, false>), dim3(nblk), dim3(512), 0, s, a);
+        if (full && g_variant != MGK_TUNE_J2_RING_OLD) {
+            LAUNCH_WX(width_1248, w, (k_jacobi2b<T, WX, false>), nblk, s, a);
         } else if (full) {
-            if (w <= 1) hipLaunchKernelGGL((k_jacobi2<T, 1, 3>), dim3(nblk), dim3(64), 0, s, a);
-            else if (w <= 2) hipLaunchKernelGGL((k_jacobi2<T, 2, 3>), dim3(nblk), dim3(128), 0, s, a);
-            else if (w <= 4) hipLaunchKernelGGL((k_jacobi2<T, 4, 3>), dim3(nblk), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_jacobi2<T, 8, 3>), dim3(nblk), dim3(512), 0, s, a);
+            LAUNCH_WX(width_1248, w, (k_jacobi2<T, WX, 3>), nblk, s, a);
         } else {
-            if (w <= 1) hipLaunchKernelGGL((k_jacobi2<T, 1, 0>), dim3(nblk), dim3(64), 0, s, a);
-            else if (w <= 2) hipLaunchKernelGGL((k_jacobi2<T, 2, 0>), dim3(nblk), dim3(128), 0, s, a);
-            else if (w <= 4) hipLaunchKernelGGL((k_jacobi2<T, 4, 0>), dim3(nblk), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_jacobi2<T, 8, 0>), dim3(nblk), dim3(512), 0, s, a);
+            LAUNCH_WX(width_1248, w, (k_jacobi2<T, WX, 0>), nblk, s, a);
         }
     } else {
         if (full) {
-            if (w <= 1) hipLaunchKernelGGL((k_jacobi2r<T, 1, 3>), dim3(nblk), dim3(64), 0, s, a);
-            else if (w <= 2) hipLaunchKernelGGL((k_jacobi2r<T, 2, 3>), dim3(nblk), dim3(128), 0, s, a);
-            else if (w <= 4) hipLaunchKernelGGL((k_jacobi2r<T, 4, 3>), dim3(nblk), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_jacobi2r<T, 8, 3>), dim3(nblk), dim3(512), 0, s, a);
+            LAUNCH_WX(width_1248, w, (k_jacobi2r<T, WX, 3>), nblk, s, a);
         } else {
-            if (w <= 1) hipLaunchKernelGGL((k_jacobi2r<T, 1, 0>), dim3(nblk), dim3(64), 0, s, a);
-            else if (w <= 2) hipLaunchKernelGGL((k_jacobi2r<T, 2, 0>), dim3(nblk), dim3(128), 0, s, a);
-            else if (w <= 4) hipLaunchKernelGGL((k_jacobi2r<T, 4, 0>), dim3(nblk), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_jacobi2r<T, 8, 0>), dim3(nblk), dim3(512), 0, s, a);
+            LAUNCH_WX(width_1248, w, (k_jacobi2r<T, WX, 0>), nblk, s, a);
         }
     }
     HIPCHK(hipGetLastError());
@@ -2326,7 +2286,7 @@ static bool j2zero_ok(const mgk_geom *g) {
     constexpr int VX = 16 / sizeof(T);
     if (!g || g->dim != 3 || (g->nx + 1) % (64 * VX) != 0 || (g->ny + 1) % 4 != 0 || g->nx + 1 > 1024) return false;
     const int w = (g->nx + 1) / (64 * VX);
-    if (g_variant == 2 || g_variant == 36 || g_variant == 37) return false;
+    if (g_variant == 2 || g_variant == MGK_TUNE_J2_REG_PRED || g_variant == MGK_TUNE_J2_RING_PRED) return false;
     return w == 1 || w == 2 || w == 4 || w == 8;                 // (fp64 rows of 1024 too: the ring form, 148 KB of LDS, only from the zero guess)
 }
 extern "C" int mgk_jacobi2_zero_ok_f64(const mgk_geom *g) { return j2zero_ok<double>(g) ? 1 : 0; }
@@ -2369,10 +2329,9 @@ extern "C" int mgk_jacobi2_sumsq_slab_f64(mgk_ctx *c, const mgk_geom *g, const m
                                           const double *b, const double *u, double *unew, const double *far, int has_lo, int has_hi,
                                           int zbeg, int zend, int part_off, int *nparts, void *stream) {
     if (!g || !nparts) return fail(MGK_EINVAL, "mgk_jacobi2_sumsq_slab_f64: bad arguments");
-    if ((has_lo || has_hi) && (!gfar || !far || gfar->dim != 3 || gfar->nz != 2 || gfar->nx != g->nx || gfar->ny != g->ny || gfar->pitch != g->pitch || g->nz < 2))
+    if ((has_lo || has_hi) && !(far_geom_ok(gfar, far, g) && g->nz >= 2))
         return fail(MGK_EINVAL, "mgk_jacobi2_sumsq_slab_f64: the far-plane field must have the geometry (nx, ny, 2) of the slab");
-    const double *lo = has_lo ? far + gfar->org - gfar->plane : nullptr;
-    const double *hi = has_hi ? far + gfar->org + 2 * gfar->plane : nullptr;
+    const double *lo = far_lo_plane(far, gfar, has_lo), *hi = far_hi_plane(far, gfar, has_hi);
     return jacobi2<double>(c, g, coef, dinv, scale, b, u, unew, lo, hi, zbeg, zend, stream, nparts, part_off);
 }
 // ... the mid-iterate form (mgk_jacobi2_sumsq_mid_f64) on the planes [zbeg, zend) of a z-slab: unew = J(J(u)), partials of || b - A J(u) ||^2
@@ -2380,10 +2339,9 @@ extern "C" int mgk_jacobi2_sumsq_mid_slab_f64(mgk_ctx *c, const mgk_geom *g, con
                                               const double *b, const double *u, double *unew, const double *far, int has_lo, int has_hi,
                                               int zbeg, int zend, int part_off, int *nparts, void *stream) {
     if (!g || !nparts) return fail(MGK_EINVAL, "mgk_jacobi2_sumsq_mid_slab_f64: bad arguments");
-    if ((has_lo || has_hi) && (!gfar || !far || gfar->dim != 3 || gfar->nz != 2 || gfar->nx != g->nx || gfar->ny != g->ny || gfar->pitch != g->pitch || g->nz < 2))
+    if ((has_lo || has_hi) && !(far_geom_ok(gfar, far, g) && g->nz >= 2))
         return fail(MGK_EINVAL, "mgk_jacobi2_sumsq_mid_slab_f64: the far-plane field must have the geometry (nx, ny, 2) of the slab");
-    const double *lo = has_lo ? far + gfar->org - gfar->plane : nullptr;
-    const double *hi = has_hi ? far + gfar->org + 2 * gfar->plane : nullptr;
+    const double *lo = far_lo_plane(far, gfar, has_lo), *hi = far_hi_plane(far, gfar, has_hi);
     return jacobi2<double>(c, g, coef, dinv, scale, b, u, unew, lo, hi, zbeg, zend, stream, nparts, part_off, false, 2);
 }
 // The same on a z-slab.  `far` is a field of geometry (nx, ny, nz = 2) whose ghost planes hold the neighbours' second plane
@@ -2392,11 +2350,9 @@ extern "C" int mgk_jacobi2_sumsq_mid_slab_f64(mgk_ctx *c, const mgk_geom *g, con
 template <typename T>
 static int jacobi2_slab(mgk_ctx *c, const mgk_geom *g, const mgk_geom *gfar, const double *coef, double dinv, double scale,
                         const T *b, const T *u, T *unew, const T *far, int has_lo, int has_hi, int zbeg, int zend, void *stream) {
-    if (!g || !gfar || !far || gfar->dim != 3 || gfar->nz != 2 || gfar->nx != g->nx || gfar->ny != g->ny || gfar->pitch != g->pitch ||
-        g->nz < 2)
+    if (!g || !far_geom_ok(gfar, far, g) || g->nz < 2)
         return fail(MGK_EINVAL, "mgk_jacobi2_slab: the far-plane field must have the geometry (nx, ny, 2) of the slab");
-    const T *lo = has_lo ? far + gfar->org - gfar->plane : nullptr;
-    const T *hi = has_hi ? far + gfar->org + 2 * gfar->plane : nullptr;
+    const T *lo = far_lo_plane(far, gfar, has_lo), *hi = far_hi_plane(far, gfar, has_hi);
     return jacobi2<T>(c, g, coef, dinv, scale, b, u, unew, lo, hi, zbeg, zend, stream);
 }
 extern "C" int mgk_jacobi2_slab_f64(mgk_ctx *c, const mgk_geom *g, const mgk_geom *gfar, const double *coef, double dinv, double scale,
@@ -2891,13 +2847,6 @@ static bool srr_shape_ok(const mgk_geom *gf, const mgk_geom *gc) {
 }
 extern "C" int mgk_sweep_residual_restrict_ok_f64(const mgk_geom *gf, const mgk_geom *gc) { return srr_shape_ok<double>(gf, gc) ? 1 : 0; }
 
-template <typename T, int TY>
-static void launch_srr(int w, unsigned nblk, hipStream_t s, const SRRArgs<T> &a) {
-    if (w <= 1) hipLaunchKernelGGL((k_srr<T, 1, TY>), dim3(nblk), dim3(64), 0, s, a);
-    else if (w <= 2) hipLaunchKernelGGL((k_srr<T, 2, TY>), dim3(nblk), dim3(128), 0, s, a);
-    else if (w <= 4) hipLaunchKernelGGL((k_srr<T, 4, TY>), dim3(nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_srr<T, 8, TY>), dim3(nblk), dim3(512), 0, s, a);
-}
 // out = J(u); bc = R (b - A out); uc0 (optional) = scale_c * (bc * dinv_c)
 static int sweep_residual_restrict(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
                                    const double *b, const double *u, double *unew, double *bc, double *uc0, double dinv_c, double scale_c,
@@ -2911,7 +2860,7 @@ static int sweep_residual_restrict(mgk_ctx *c, const mgk_geom *gf, const mgk_geo
     a.u = u + gf->org; a.b = b + gf->org; a.out = unew + gf->org; a.bc = bc + gc->org; a.uc0 = uc0 ? uc0 + gc->org : nullptr;
     a.nx = gf->nx; a.ny = gf->ny; a.nz = gf->nz; a.nxc = gc->nx; a.nyc = gc->ny; a.nzc = gc->nz;
     a.rs = gf->pitch; a.ms = gf->plane; a.crs = gc->pitch; a.cms = gc->plane;
-    a.a0 = coef[0]; a.a1 = coef[1]; a.a2 = coef[2]; a.a3 = coef[3]; a.a4 = coef[4]; a.a5 = coef[5]; a.a6 = coef[6];
+    set_coef7(a, coef);
     a.dinv = dinv; a.scale = scale; a.dinv_c = dinv_c; a.scale_c = scale_c;
     a.far_lo = far_lo; a.far_hi = far_hi; a.far2_hi = far2_hi; a.bfar_hi = bfar_hi;
     a.has_lo = far_lo != nullptr; a.has_hi = far_hi != nullptr;
@@ -2921,28 +2870,18 @@ static int sweep_residual_restrict(mgk_ctx *c, const mgk_geom *gf, const mgk_geo
     const int nkc = kcend - kcbeg;
     // tiles of 4 rows with the swept planes in LDS (1023^3: 5.3 ms against 6.2 ms for tiles of 2 rows with them in registers;
     // 511^3: 0.72 against 0.82; tiles of 4 rows all in registers need 316 VGPRs at 8 waves).  Rows of <= 2 waves (n <= 255): tiles of
-    // 2 rows, two blocks per CU -- 255^3 0.119 against 0.136 ms.  Tuning variants: 40 forces tiles of 2 rows, 41 tiles of 4
-    const int TYsel = slab ? 4 : (g_variant == 40) ? 2 : (g_variant == 41) ? 4 : (w >= 4 ? 4 : 2);
+    // 2 rows, two blocks per CU -- 255^3 0.119 against 0.136 ms.  MGK_TUNE_SRR_TY2 / _TY4 force tiles of 2 / of 4 rows
+    const int TYsel = slab ? 4 : (g_variant == MGK_TUNE_SRR_TY2) ? 2 : (g_variant == MGK_TUNE_SRR_TY4) ? 4 : (w >= 4 ? 4 : 2);
     a.nty = (gf->ny + TYsel - 1) / TYsel;
     // blocks: a multiple of what the chip holds at once (512-thread blocks: one per CU); every chunk recomputes three planes
     // (rows of one wave, 127^3: 2048 one-wave blocks of 2 coarse planes instead of 1024 of 4 -- 34.2 -> 28.5 us inside the 257^3 cycle)
     const long target = (w > 4) ? (TYsel == 4 ? 256 : 512) : (w <= 1 ? 2048 : 1024);
-    long nch = (a.nty >= target) ? 1 : (target + a.nty - 1) / a.nty;
-    if (g_zchunk > 0) nch = (nkc + g_zchunk - 1) / g_zchunk;
-    else if (slab && c->chunk_planes > 0 && nch < (2 * nkc + c->chunk_planes - 1) / c->chunk_planes) nch = (2 * nkc + c->chunk_planes - 1) / c->chunk_planes;
-    int kcc = (int)((nkc + nch - 1) / nch);
-    const int kmin = (w <= 1) ? 2 : 4;
-    if (kcc < kmin && g_zchunk <= 0) kcc = kmin;
-    if (kcc > nkc) kcc = nkc;
-    a.kcc = kcc;
-    const unsigned nblk = (unsigned)(a.nty * ((nkc + kcc - 1) / kcc));
-    if (TYsel == 4) {
-        hipStream_t st = S(c, stream);
-        if (w <= 1) hipLaunchKernelGGL((k_srr4b<1>), dim3(nblk), dim3(64), 0, st, a);
-        else if (w <= 2) hipLaunchKernelGGL((k_srr4b<2>), dim3(nblk), dim3(128), 0, st, a);
-        else if (w <= 4) hipLaunchKernelGGL((k_srr4b<4>), dim3(nblk), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_srr4b<8>), dim3(nblk), dim3(512), 0, st, a);
-    } else launch_srr<T, 2>(w, nblk, S(c, stream), a);
+    // coarse planes: a slab's chunk_planes hint counts fine planes (2 per coarse plane); an explicit chunk may be shorter than the minimum
+    const Chunks ch = cut_chunks(c, nkc, a.nty, target, {/*min*/ (w <= 1) ? 2 : 4, true, /*even*/ false, /*clamp*/ true, /*hint*/ 2, slab ? 1 : 0});
+    a.kcc = ch.len;
+    const unsigned nblk = (unsigned)(a.nty * ch.count);
+    if (TYsel == 4) LAUNCH_WX(width_1248, w, (k_srr4b<WX>), nblk, S(c, stream), a);
+    else LAUNCH_WX(width_1248, w, (k_srr<T, WX, 2>), nblk, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2969,14 +2908,12 @@ extern "C" int mgk_sweep_residual_restrict_slab_f64(mgk_ctx *c, const mgk_geom *
                                                     const double *far, const double *far2, const double *bfar, int has_lo, int has_hi,
                                                     double *bc, int kcbeg, int kcend, void *stream) {
     if (!mgk_sweep_residual_restrict_slab_ok_f64(gf, gc)) return fail(MGK_EINVAL, "mgk_sweep_residual_restrict_slab_f64: shape not built");
-    if ((has_lo || has_hi) && (!gfar || !far || gfar->dim != 3 || gfar->nz != 2 || gfar->nx != gf->nx || gfar->ny != gf->ny || gfar->pitch != gf->pitch))
+    if ((has_lo || has_hi) && !far_geom_ok(gfar, far, gf))
         return fail(MGK_EINVAL, "mgk_sweep_residual_restrict_slab_f64: the far-plane fields must have the geometry (nx, ny, 2) of the slab");
     if (has_hi && (!far2 || !bfar || gf->nz != 2 * gc->nz)) return fail(MGK_EINVAL, "mgk_sweep_residual_restrict_slab_f64: a slab with a rank above has nzf = 2 nzc and needs far2 / bfar");
     if (!has_hi && gf->nz != 2 * gc->nz + 1) return fail(MGK_EINVAL, "mgk_sweep_residual_restrict_slab_f64: the last slab has nzf = 2 nzc + 1");
-    const double *lo = has_lo ? far + gfar->org - gfar->plane : nullptr;
-    const double *hi = has_hi ? far + gfar->org + 2 * gfar->plane : nullptr;
-    const double *hi2 = has_hi ? far2 + gfar->org + 2 * gfar->plane : nullptr;
-    const double *bhi = has_hi ? bfar + gfar->org + 2 * gfar->plane : nullptr;
+    const double *lo = far_lo_plane(far, gfar, has_lo), *hi = far_hi_plane(far, gfar, has_hi);
+    const double *hi2 = far_hi_plane(far2, gfar, has_hi), *bhi = far_hi_plane(bfar, gfar, has_hi);      // (far2, bfar: fields of the same geometry)
     return sweep_residual_restrict(c, gf, gc, coef, dinv, scale, b, u, unew, bc, nullptr, 0.0, 0.0, lo, hi, hi2, bhi, kcbeg, kcend, stream);
 }
 
@@ -3092,17 +3029,13 @@ static int jacobi2_2d(mgk_ctx *c, const mgk_geom *g, const double *coef, double 
     J2dArgs a; memset(&a, 0, sizeof(a));
     a.u = u + g->org; a.b = b + g->org; a.out = unew + g->org;
     a.nx = g->nx; a.ny = g->ny; a.rs = g->pitch;
-    if (coef) { a.a0 = coef[0]; a.a2 = coef[1]; a.a3 = coef[2]; a.a4 = coef[3]; a.a6 = coef[4]; }
+    if (coef) set_coef5(a, coef);
     a.dinv = dinv; a.scale = scale; a.ctab = ctab; a.dtab = dtab;
     constexpr int WX = 4, TXE = 2 * (64 * WX - 2);
     a.ntx = (g->nx + TXE - 1) / TXE;
-    long nch = (2048 + a.ntx - 1) / a.ntx;
-    if (g_zchunk > 0) nch = (g->ny + g_zchunk - 1) / g_zchunk;
-    int yc = (int)((g->ny + nch - 1) / nch);
-    if (yc < 16) yc = 16;
-    if (yc > g->ny) yc = g->ny;
-    a.yc = yc;
-    const long nty = (g->ny + yc - 1) / yc;
+    const Chunks ch = cut_chunks(c, g->ny, a.ntx, 2048, {/*min*/ 16, false, /*even*/ false, /*clamp*/ true, /*hint*/ 0, 0});
+    a.yc = ch.len;
+    const long nty = ch.count;
     if (norm_parts) {
         if (a.ntx * nty > c->max_partials) return fail(MGK_EINVAL, "mgk_jacobi2_2d_sumsq_f64: more blocks than partial slots");
         a.partials = c->partials;
@@ -3260,15 +3193,19 @@ static void row_grid(const RowArgs &a, int cols, dim3 &grid, dim3 &block, int ma
     grid = dim3(gx, (unsigned)gy);
 }
 
-extern "C" int mgk_jacobi_zero_f64(mgk_ctx *c, const mgk_geom *g, double dinv, double scale,
-                                   const double *b, double *unew, void *stream) {
-    if (!c || !g || !b || !unew) return fail(MGK_EINVAL, "mgk_jacobi_zero_f64: bad arguments");
+template <typename T>
+static int jacobi_zero(mgk_ctx *c, const mgk_geom *g, double dinv, double scale, const T *b, T *unew, void *stream, const char *bad) {
+    if (!c || !g || !b || !unew) return fail(MGK_EINVAL, bad);
     RowArgs a = row_args(g);
     dim3 grid, block;
     row_grid(a, a.npairs, grid, block, 1024);
-    hipLaunchKernelGGL(k_jacobi_zero<double>, grid, block, 0, S(c, stream), a, dinv, scale, b + g->org, unew + g->org, (const double *)nullptr);
+    hipLaunchKernelGGL(k_jacobi_zero<T>, grid, block, 0, S(c, stream), a, (T)dinv, (T)scale, b + g->org, unew + g->org, (const T *)nullptr);
     HIPCHK(hipGetLastError());
     return 0;
+}
+extern "C" int mgk_jacobi_zero_f64(mgk_ctx *c, const mgk_geom *g, double dinv, double scale,
+                                   const double *b, double *unew, void *stream) {
+    return jacobi_zero<double>(c, g, dinv, scale, b, unew, stream, "mgk_jacobi_zero_f64: bad arguments");
 }
 
 extern "C" int mgk_sumsq_f64(mgk_ctx *c, const mgk_geom *g, const double *x, double *sumsq_host, void *stream) {
@@ -3435,24 +3372,24 @@ static int xfer_args(const mgk_geom *gf, const mgk_geom *gc, XferArgs &a) {
     return 0;
 }
 
-extern "C" int mgk_restrict_fw_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc,
-                                   const double *rf, double *bc, void *stream) {
-    if (!c || !gf || !gc || !rf || !bc) return fail(MGK_EINVAL, "mgk_restrict_fw_f64: bad arguments");
+// full weighting / prolongation + correction as kernels of their own (fp32: 3-D only); one block row per 1024 / grid.x rows at the most
+template <typename T>
+static int restrict_fw(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const T *rf, T *bc, void *stream, const char *bad) {
+    if (!c || !gf || !gc || !rf || !bc || (sizeof(T) != 8 && gf->dim != 3)) return fail(MGK_EINVAL, bad);
     XferArgs a;
     int rc = xfer_args(gf, gc, a);
     if (rc) return rc;
     dim3 block(256), grid((gc->nx + 1 + 255) / 256, 1);
     long rows = (long)gc->ny * gc->nz, cap = 1024 / grid.x; if (cap < 1) cap = 1;
     grid.y = (unsigned)(rows < cap ? rows : cap);
-    if (gf->dim == 3) hipLaunchKernelGGL((k_restrict<double, 3>), grid, block, 0, S(c, stream), a, rf + gf->org, bc + gc->org);
-    else hipLaunchKernelGGL((k_restrict<double, 2>), grid, block, 0, S(c, stream), a, rf + gf->org, bc + gc->org);
+    if (gf->dim == 3) hipLaunchKernelGGL((k_restrict<T, 3>), grid, block, 0, S(c, stream), a, rf + gf->org, bc + gc->org);
+    else if constexpr (sizeof(T) == 8) hipLaunchKernelGGL((k_restrict<T, 2>), grid, block, 0, S(c, stream), a, rf + gf->org, bc + gc->org);
     HIPCHK(hipGetLastError());
     return 0;
 }
-
-extern "C" int mgk_prolong_add_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc,
-                                   const double *uc, double *uf, void *stream) {
-    if (!c || !gf || !gc || !uc || !uf) return fail(MGK_EINVAL, "mgk_prolong_add_f64: bad arguments");
+template <typename T>
+static int prolong_add(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const T *uc, T *uf, void *stream, const char *bad) {
+    if (!c || !gf || !gc || !uc || !uf || (sizeof(T) != 8 && gf->dim != 3)) return fail(MGK_EINVAL, bad);
     XferArgs a;
     int rc = xfer_args(gf, gc, a);
     if (rc) return rc;
@@ -3460,10 +3397,16 @@ extern "C" int mgk_prolong_add_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geo
     dim3 block(256), grid((npairs + 255) / 256, 1);
     long rows = (long)gf->ny * gf->nz, cap = 1024 / grid.x; if (cap < 1) cap = 1;
     grid.y = (unsigned)(rows < cap ? rows : cap);
-    if (gf->dim == 3) hipLaunchKernelGGL((k_prolong_add<double, 3>), grid, block, 0, S(c, stream), a, uc + gc->org, uf + gf->org);
-    else hipLaunchKernelGGL((k_prolong_add<double, 2>), grid, block, 0, S(c, stream), a, uc + gc->org, uf + gf->org);
+    if (gf->dim == 3) hipLaunchKernelGGL((k_prolong_add<T, 3>), grid, block, 0, S(c, stream), a, uc + gc->org, uf + gf->org);
+    else if constexpr (sizeof(T) == 8) hipLaunchKernelGGL((k_prolong_add<T, 2>), grid, block, 0, S(c, stream), a, uc + gc->org, uf + gf->org);
     HIPCHK(hipGetLastError());
     return 0;
+}
+extern "C" int mgk_restrict_fw_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *rf, double *bc, void *stream) {
+    return restrict_fw<double>(c, gf, gc, rf, bc, stream, "mgk_restrict_fw_f64: bad arguments");
+}
+extern "C" int mgk_prolong_add_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *uc, double *uf, void *stream) {
+    return prolong_add<double>(c, gf, gc, uc, uf, stream, "mgk_prolong_add_f64: bad arguments");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3705,14 +3648,8 @@ extern "C" int mgk_geom_init_f32(mgk_geom *g, int dim, int nx, int ny, int nz) {
 
 extern "C" int mgk_jacobi_range_f32(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                                     const float *b, const float *u, float *unew, int zbeg, int zend, void *stream) {
-    if (!c || !g || !coef || !b || !u || !unew || u == unew) return fail(MGK_EINVAL, "mgk_jacobi_f32: bad arguments");
-    if (zbeg < 0 || zend > g->nz || zbeg >= zend) return fail(MGK_EINVAL, "mgk_jacobi_range_f32: empty or out-of-range plane range");
-    StArgs<float> a; memset(&a, 0, sizeof(a));
-    a.u = u + g->org; a.b = b + g->org; a.out = unew + g->org;
-    set_coef(a, g, coef); a.dinv = (float)dinv; a.scale = (float)scale;
-    a.zbeg = zbeg; a.zend = zend;
-    if (jrow_ok<float>(g)) return launch_jrow<float, false>(c, g, a, zbeg, zend, S(c, stream), nullptr, 0, nullptr);
-    return dispatch_st<MODE_JACOBI>(c, g, a, S(c, stream), nullptr);
+    return jacobi_range<float>(c, g, coef, dinv, scale, b, u, unew, zbeg, zend, stream, "mgk_jacobi_f32: bad arguments",
+                               "mgk_jacobi_range_f32: empty or out-of-range plane range");
 }
 extern "C" int mgk_jacobi_f32(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                               const float *b, const float *u, float *unew, void *stream) {
@@ -3721,13 +3658,8 @@ extern "C" int mgk_jacobi_f32(mgk_ctx *c, const mgk_geom *g, const double *coef,
 }
 extern "C" int mgk_residual_range_f32(mgk_ctx *c, const mgk_geom *g, const double *coef,
                                       const float *b, const float *u, float *r, int zbeg, int zend, void *stream) {
-    if (!c || !g || !coef || !b || !u || !r || u == r) return fail(MGK_EINVAL, "mgk_residual_f32: bad arguments");
-    if (zbeg < 0 || zend > g->nz || zbeg >= zend) return fail(MGK_EINVAL, "mgk_residual_range_f32: empty or out-of-range plane range");
-    StArgs<float> a; memset(&a, 0, sizeof(a));
-    a.u = u + g->org; a.b = b + g->org; a.out = r + g->org;
-    set_coef(a, g, coef);
-    a.zbeg = zbeg; a.zend = zend;
-    return dispatch_st<MODE_RESIDUAL>(c, g, a, S(c, stream), nullptr);
+    return residual_range<float>(c, g, coef, b, u, r, zbeg, zend, stream, "mgk_residual_f32: bad arguments",
+                                 "mgk_residual_range_f32: empty or out-of-range plane range");
 }
 extern "C" int mgk_residual_f32(mgk_ctx *c, const mgk_geom *g, const double *coef,
                                 const float *b, const float *u, float *r, void *stream) {
@@ -3736,57 +3668,37 @@ extern "C" int mgk_residual_f32(mgk_ctx *c, const mgk_geom *g, const double *coe
 }
 extern "C" int mgk_jacobi_zero_f32(mgk_ctx *c, const mgk_geom *g, double dinv, double scale,
                                    const float *b, float *unew, void *stream) {
-    if (!c || !g || !b || !unew) return fail(MGK_EINVAL, "mgk_jacobi_zero_f32: bad arguments");
-    RowArgs a = row_args(g);
-    dim3 grid, block;
-    row_grid(a, a.npairs, grid, block, 1024);
-    hipLaunchKernelGGL(k_jacobi_zero<float>, grid, block, 0, S(c, stream), a, (float)dinv, (float)scale, b + g->org, unew + g->org, (const float *)nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return jacobi_zero<float>(c, g, dinv, scale, b, unew, stream, "mgk_jacobi_zero_f32: bad arguments");
 }
-extern "C" int mgk_restrict_fw_f32(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc,
-                                   const float *rf, float *bc, void *stream) {
-    if (!c || !gf || !gc || !rf || !bc || gf->dim != 3) return fail(MGK_EINVAL, "mgk_restrict_fw_f32: bad arguments");
-    XferArgs a;
-    int rc = xfer_args(gf, gc, a);
-    if (rc) return rc;
-    dim3 block(256), grid((gc->nx + 1 + 255) / 256, 1);
-    long rows = (long)gc->ny * gc->nz, cap = 1024 / grid.x; if (cap < 1) cap = 1;
-    grid.y = (unsigned)(rows < cap ? rows : cap);
-    hipLaunchKernelGGL((k_restrict<float, 3>), grid, block, 0, S(c, stream), a, rf + gf->org, bc + gc->org);
-    HIPCHK(hipGetLastError());
-    return 0;
+extern "C" int mgk_restrict_fw_f32(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const float *rf, float *bc, void *stream) {
+    return restrict_fw<float>(c, gf, gc, rf, bc, stream, "mgk_restrict_fw_f32: bad arguments");
 }
-extern "C" int mgk_prolong_add_f32(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc,
-                                   const float *uc, float *uf, void *stream) {
-    if (!c || !gf || !gc || !uc || !uf || gf->dim != 3) return fail(MGK_EINVAL, "mgk_prolong_add_f32: bad arguments");
-    XferArgs a;
-    int rc = xfer_args(gf, gc, a);
-    if (rc) return rc;
-    const int npairs = (gf->nx + 1) / 2;
-    dim3 block(256), grid((npairs + 255) / 256, 1);
-    long rows = (long)gf->ny * gf->nz, cap = 1024 / grid.x; if (cap < 1) cap = 1;
-    grid.y = (unsigned)(rows < cap ? rows : cap);
-    hipLaunchKernelGGL((k_prolong_add<float, 3>), grid, block, 0, S(c, stream), a, uc + gc->org, uf + gf->org);
-    HIPCHK(hipGetLastError());
-    return 0;
+extern "C" int mgk_prolong_add_f32(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const float *uc, float *uf, void *stream) {
+    return prolong_add<float>(c, gf, gc, uc, uf, stream, "mgk_prolong_add_f32: bad arguments");
 }
 
 // fp64 residual r = b - A u, written as fp32 (the right-hand side of the fp32 correction cycle) and reduced
 // to sum r^2 in fp64 in the same pass: reads 16 B, writes 4 B per unknown
+// body of the four bridge passes: e32 != NULL: the corrected u is written to unew first (MODE_CRES32); e0 != NULL: the _jz forms
+static int bridge_residual(mgk_ctx *c, const mgk_geom *g, const mgk_geom *g32, const double *coef, const double *b, const double *u,
+                           const float *e32, double *unew, float *r32, float *e0, double dinv, double scale, double *sumsq_host, void *stream) {
+    StArgs<double> a; memset(&a, 0, sizeof(a));
+    a.u = u + g->org; a.b = b + g->org; a.out32 = r32 + g32->org; a.ors = g32->pitch; a.oms = g32->plane;
+    if (e32) { a.out = unew + g->org; a.e32 = e32 + g32->org; }
+    if (e0) { a.jz32 = e0 + g32->org; a.dinv32 = (float)dinv; a.scale32 = (float)scale; }
+    a.partials = c->partials;
+    set_coef(a, g, coef);
+    int nblk = 0;
+    int rc = e32 ? dispatch_st<MODE_CRES32>(c, g, a, S(c, stream), &nblk) : dispatch_st<MODE_RES32>(c, g, a, S(c, stream), &nblk);
+    if (rc) return rc;
+    return finish_to_host(c, nblk, 1, S(c, stream), sumsq_host);
+}
 extern "C" int mgk_residual_f64_to_f32(mgk_ctx *c, const mgk_geom *g, const mgk_geom *g32, const double *coef,
                                        const double *b, const double *u, float *r32, double *sumsq_host, void *stream) {
     if (!c || !g || !g32 || !coef || !b || !u || !r32 || !sumsq_host || g->dim != 3 ||
         g->nx != g32->nx || g->ny != g32->ny || g->nz != g32->nz)
         return fail(MGK_EINVAL, "mgk_residual_f64_to_f32: bad arguments");
-    StArgs<double> a; memset(&a, 0, sizeof(a));
-    a.u = u + g->org; a.b = b + g->org; a.out32 = r32 + g32->org; a.ors = g32->pitch; a.oms = g32->plane;
-    a.partials = c->partials;
-    set_coef(a, g, coef);
-    int nblk = 0;
-    int rc = dispatch_st<MODE_RES32>(c, g, a, S(c, stream), &nblk);
-    if (rc) return rc;
-    return finish_to_host(c, nblk, 1, S(c, stream), sumsq_host);
+    return bridge_residual(c, g, g32, coef, b, u, nullptr, nullptr, r32, nullptr, 0.0, 0.0, sumsq_host, stream);
 }
 
 // the same, also writing e0 = scale32 * (r32 * dinv32): the first sweep of the fp32 correction cycle from its zero guess (what
@@ -3797,15 +3709,7 @@ extern "C" int mgk_residual_f64_to_f32_jz(mgk_ctx *c, const mgk_geom *g, const m
     if (!c || !g || !g32 || !coef || !b || !u || !r32 || !e0 || e0 == r32 || !sumsq_host || g->dim != 3 ||
         g->nx != g32->nx || g->ny != g32->ny || g->nz != g32->nz)
         return fail(MGK_EINVAL, "mgk_residual_f64_to_f32_jz: bad arguments");
-    StArgs<double> a; memset(&a, 0, sizeof(a));
-    a.u = u + g->org; a.b = b + g->org; a.out32 = r32 + g32->org; a.ors = g32->pitch; a.oms = g32->plane;
-    a.jz32 = e0 + g32->org; a.dinv32 = (float)dinv; a.scale32 = (float)scale;
-    a.partials = c->partials;
-    set_coef(a, g, coef);
-    int nblk = 0;
-    int rc = dispatch_st<MODE_RES32>(c, g, a, S(c, stream), &nblk);
-    if (rc) return rc;
-    return finish_to_host(c, nblk, 1, S(c, stream), sumsq_host);
+    return bridge_residual(c, g, g32, coef, b, u, nullptr, nullptr, r32, e0, dinv, scale, sumsq_host, stream);
 }
 
 // The whole outer step of the mixed-precision iteration in one pass: unew = u + (double) e32 (written), r32 = (float)(b - A unew),
@@ -3817,15 +3721,7 @@ extern "C" int mgk_correct_residual_f64_f32(mgk_ctx *c, const mgk_geom *g, const
     if (!c || !g || !g32 || !coef || !b || !u || !e32 || !unew || !r32 || !sumsq_host || u == unew || (const float *)r32 == e32 ||
         g->dim != 3 || g->nx != g32->nx || g->ny != g32->ny || g->nz != g32->nz)
         return fail(MGK_EINVAL, "mgk_correct_residual_f64_f32: bad arguments");
-    StArgs<double> a; memset(&a, 0, sizeof(a));
-    a.u = u + g->org; a.b = b + g->org; a.out = unew + g->org;
-    a.out32 = r32 + g32->org; a.e32 = e32 + g32->org; a.ors = g32->pitch; a.oms = g32->plane;
-    a.partials = c->partials;
-    set_coef(a, g, coef);
-    int nblk = 0;
-    int rc = dispatch_st<MODE_CRES32>(c, g, a, S(c, stream), &nblk);
-    if (rc) return rc;
-    return finish_to_host(c, nblk, 1, S(c, stream), sumsq_host);
+    return bridge_residual(c, g, g32, coef, b, u, e32, unew, r32, nullptr, 0.0, 0.0, sumsq_host, stream);
 }
 
 extern "C" int mgk_correct_residual_f64_f32_jz(mgk_ctx *c, const mgk_geom *g, const mgk_geom *g32, const double *coef,
@@ -3834,16 +3730,7 @@ extern "C" int mgk_correct_residual_f64_f32_jz(mgk_ctx *c, const mgk_geom *g, co
     if (!c || !g || !g32 || !coef || !b || !u || !e32 || !unew || !r32 || !e0 || e0 == r32 || (const float *)e0 == e32 || !sumsq_host ||
         u == unew || (const float *)r32 == e32 || g->dim != 3 || g->nx != g32->nx || g->ny != g32->ny || g->nz != g32->nz)
         return fail(MGK_EINVAL, "mgk_correct_residual_f64_f32_jz: bad arguments");
-    StArgs<double> a; memset(&a, 0, sizeof(a));
-    a.u = u + g->org; a.b = b + g->org; a.out = unew + g->org;
-    a.out32 = r32 + g32->org; a.e32 = e32 + g32->org; a.ors = g32->pitch; a.oms = g32->plane;
-    a.jz32 = e0 + g32->org; a.dinv32 = (float)dinv; a.scale32 = (float)scale;
-    a.partials = c->partials;
-    set_coef(a, g, coef);
-    int nblk = 0;
-    int rc = dispatch_st<MODE_CRES32>(c, g, a, S(c, stream), &nblk);
-    if (rc) return rc;
-    return finish_to_host(c, nblk, 1, S(c, stream), sumsq_host);
+    return bridge_residual(c, g, g32, coef, b, u, e32, unew, r32, e0, dinv, scale, sumsq_host, stream);
 }
 
 // u64 += (double) e32  (the fp64 correction step)
@@ -4632,27 +4519,29 @@ __global__ void __launch_bounds__(64 * WX) k_jrow(const PJArgs<T> a, double *par
         if (threadIdx.x == 0) partials[blockIdx.x] = s;
     }
 }
-template <typename T, bool NORM>
-static int launch_jrow(mgk_ctx *c, const mgk_geom *g, const StArgs<T> &a, int zbeg, int zend, hipStream_t s, double *partials, int max_partials, int *nparts) {
-    constexpr int VX = 16 / sizeof(T);
-    const int w = (g->nx + 1) / (64 * VX);
+// the row kernels' arguments from those of the marching kernel: fields, fine geometry, coefficients, plane range, tiles of 4 rows
+template <typename T>
+static PJArgs<T> pj_from_st(const StArgs<T> &a, const mgk_geom *g, int zbeg, int zend) {
     PJArgs<T> q; memset(&q, 0, sizeof(q));
     q.u = a.u; q.b = a.b; q.out = a.out;
     q.nx = g->nx; q.ny = g->ny; q.nz = g->nz; q.rs = g->pitch; q.ms = g->plane;
     q.a0 = a.a0; q.a1 = a.a1; q.a2 = a.a2; q.a3 = a.a3; q.a4 = a.a4; q.a5 = a.a5; q.a6 = a.a6; q.dinv = a.dinv; q.scale = a.scale;
     q.zbeg = zbeg; q.zend = zend;
     q.nty = (g->ny + 3) / 4;
+    return q;
+}
+template <typename T, bool NORM>
+static int launch_jrow(mgk_ctx *c, const mgk_geom *g, const StArgs<T> &a, int zbeg, int zend, hipStream_t s, double *partials, int max_partials, int *nparts) {
+    constexpr int VX = 16 / sizeof(T);
+    const int w = (g->nx + 1) / (64 * VX);
+    PJArgs<T> q = pj_from_st(a, g, zbeg, zend);
     const int nzr = zend - zbeg;
     // 512-thread blocks: one per CU (256 tiles at 1023^3, one chunk); smaller blocks several per CU.  Small levels: short chunks
     const long target = (w > 4) ? 256 : (w > 2 ? 512 : 1024);
-    long nch = (q.nty >= target) ? 1 : (target + q.nty - 1) / q.nty;
-    if (g_zchunk > 0) nch = (nzr + g_zchunk - 1) / g_zchunk;
-    else if (c->chunk_planes > 0 && nch < (nzr + c->chunk_planes - 1) / c->chunk_planes) nch = (nzr + c->chunk_planes - 1) / c->chunk_planes;
-    int zc = (int)((nzr + nch - 1) / nch);
-    if (zc < 4) zc = 4;
-    if (zc > nzr) zc = nzr;
-    long nblk = (long)q.nty * ((nzr + zc - 1) / zc);
-    if (NORM && nblk > max_partials) {
+    const Chunks ch = cut_chunks(c, nzr, q.nty, target, {/*min*/ 4, false, /*even*/ false, /*clamp*/ true, /*hint*/ 1, 1});
+    int zc = ch.len;
+    long nblk = (long)q.nty * ch.count;
+    if (NORM && nblk > max_partials) {                       // fewer, longer chunks so that the partial buffer suffices
         const long ntz = max_partials / q.nty;
         if (ntz < 1) return fail(MGK_EINVAL, "row sweep: partial buffer too small");
         zc = (int)((nzr + ntz - 1) / ntz);
@@ -4660,12 +4549,7 @@ static int launch_jrow(mgk_ctx *c, const mgk_geom *g, const StArgs<T> &a, int zb
     }
     q.zc = zc;
     if (nparts) *nparts = (int)nblk;
-#define JROW_LAUNCH(WXV) hipLaunchKernelGGL((k_jrow<T, WXV, (sizeof(T) == 8 ? 2 : 1), NORM>), dim3((unsigned)nblk), dim3(64 * WXV), 0, s, q, partials)
-    if (w <= 1) JROW_LAUNCH(1);
-    else if (w <= 2) JROW_LAUNCH(2);
-    else if (w <= 4) JROW_LAUNCH(4);
-    else JROW_LAUNCH(8);
-#undef JROW_LAUNCH
+    LAUNCH_WX(width_1248, w, (k_jrow<T, WX, (sizeof(T) == 8 ? 2 : 1), NORM>), nblk, s, q, partials);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -4693,7 +4577,6 @@ __global__ void __launch_bounds__(256) k_restrict_finish(XferArgs a, const T *rg
 // and DPP lane shifts wherever the shape allows them (measured on MI355X, LDS-tile form -> row form: fp64 fused prolongation sweep
 // 1023^3 5.36 -> 4.45 ms, 511^3 0.77 -> 0.56, 255^3 0.117 -> 0.070; fused residual + restriction 1023^3 3.74-4.04 -> 3.35 ms,
 // 255^3 0.086 -> 0.065; fp32 1023^3 2.88 -> 2.40 / 1.81 -> 1.80 ms, 511^3 0.44 -> 0.30 / 0.36 -> 0.25)
-static int row_form_default(int w, size_t esz) { (void)w; (void)esz; return 34; }
 // the row kernels load unconditionally: full rows (nx + 1 a whole number of wave rows, at most 8) and ny + 1 a multiple of 4
 template <typename T>
 static bool row_shape_ok(const mgk_geom *g) {
@@ -4701,29 +4584,30 @@ static bool row_shape_ok(const mgk_geom *g) {
     const int w = (g->nx + 1) / WR;
     return g->dim == 3 && (g->nx + 1) % WR == 0 && (w == 1 || w == 2 || w == 4 || w == 8) && (g->ny + 1) % 4 == 0 && g->ny >= 3;
 }
-// tuning variants: 30 LDS-tile kernels; 31 row kernels; 33 / 34 / 35 experimental forms of the row kernels (see the launchers)
-static int row_form(int w, size_t esz) {
-    return (g_variant >= 31 && g_variant <= 35) ? g_variant : (g_variant == 30) ? 0 : row_form_default(w, esz);
+// MGK_TUNE_LDS_TILE: the LDS-tile kernels; MGK_TUNE_ROW .. MGK_TUNE_ROW_PRED_DPP: that form of the row kernels (see the launchers); open: ROW_DPP
+enum RowForm { ROW_NONE = 0, ROW_BPERMUTE, ROW_UNCOND, ROW_DPP, ROW_PRED_DPP };
+static RowForm row_form() {
+    switch (g_variant) {
+        case MGK_TUNE_LDS_TILE: return ROW_NONE;
+        case MGK_TUNE_ROW: case MGK_TUNE_ROW_PD2: return ROW_BPERMUTE;
+        case MGK_TUNE_ROW_UNCOND: return ROW_UNCOND;
+        case MGK_TUNE_ROW_PRED_DPP: return ROW_PRED_DPP;
+        default: return ROW_DPP;
+    }
 }
 // (measured on one box, LDS-tile kernel -> row form: fp64 1023^3 sweep 4.48 -> 4.30 ms, sweep+norm 4.48 -> 4.36; 511^3 0.534 -> 0.543,
-//  255^3 0.064 -> 0.066; fp32 1023^3 2.1 -> 2.3: the row form is the default for fp64 rows of 1024 only, tuning variant 34 forces it)
+//  255^3 0.064 -> 0.066; fp32 1023^3 2.1 -> 2.3: the row form is the default for fp64 rows of 1024 only, MGK_TUNE_ROW_DPP forces it)
 template <typename T> static bool jrow_ok(const mgk_geom *g) {
     if (!row_shape_ok<T>(g) || g->nx < 127) return false;
-    return g_variant == 34 || (g_variant < 0 && sizeof(T) == 8 && g->nx + 1 >= 1024);
+    return g_variant == MGK_TUNE_ROW_DPP || (g_variant < 0 && sizeof(T) == 8 && g->nx + 1 >= 1024);
 }
 template <typename T, int PD, int FORM>
 static void launch_rrrow(int w, unsigned nblk, hipStream_t s, const RRArgs<T> &a) {
-    if (w <= 1) hipLaunchKernelGGL((k_rrrow<T, 1, PD, FORM>), dim3(nblk), dim3(64), 0, s, a);
-    else if (w <= 2) hipLaunchKernelGGL((k_rrrow<T, 2, PD, FORM>), dim3(nblk), dim3(128), 0, s, a);
-    else if (w <= 4) hipLaunchKernelGGL((k_rrrow<T, 4, PD, FORM>), dim3(nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_rrrow<T, 8, PD, FORM>), dim3(nblk), dim3(512), 0, s, a);
+    LAUNCH_WX(width_1248, w, (k_rrrow<T, WX, PD, FORM>), nblk, s, a);
 }
 template <typename T, int PD, int FORM>
 static void launch_pjrow(int w, unsigned nblk, hipStream_t s, const PJArgs<T> &a) {
-    if (w <= 1) hipLaunchKernelGGL((k_pjrow<T, 1, PD, FORM>), dim3(nblk), dim3(64), 0, s, a);
-    else if (w <= 2) hipLaunchKernelGGL((k_pjrow<T, 2, PD, FORM>), dim3(nblk), dim3(128), 0, s, a);
-    else if (w <= 4) hipLaunchKernelGGL((k_pjrow<T, 4, PD, FORM>), dim3(nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_pjrow<T, 8, PD, FORM>), dim3(nblk), dim3(512), 0, s, a);
+    LAUNCH_WX(width_1248, w, (k_pjrow<T, WX, PD, FORM>), nblk, s, a);
 }
 template <typename T>
 static int residual_restrict(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef,
@@ -4742,7 +4626,7 @@ static int residual_restrict(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc,
     a.u = u + gf->org; a.b = b + gf->org; a.bc = bc + gc->org;
     a.nx = gf->nx; a.ny = gf->ny; a.nz = gf->nz; a.nxc = gc->nx; a.nyc = gc->ny; a.nzc = gc->nz;
     a.rs = gf->pitch; a.ms = gf->plane; a.crs = gc->pitch; a.cms = gc->plane;
-    a.a0 = (T)coef[0]; a.a1 = (T)coef[1]; a.a2 = (T)coef[2]; a.a3 = (T)coef[3]; a.a4 = (T)coef[4]; a.a5 = (T)coef[5]; a.a6 = (T)coef[6];
+    set_coef7(a, coef);
     if (uc0 && gf->nz != 2 * gc->nz + 1) return fail(MGK_EINVAL, "mgk_residual_restrict_jz: whole grids only");
     a.uc0 = uc0 ? uc0 + gc->org : nullptr; a.dinv_c = (T)dinv_c; a.scale_c = (T)scale_c;
     a.far_hi = (gf->nz == 2 * gc->nz) ? far_hi : nullptr;         // only an inner slab has a plane nz + 1 to look at
@@ -4755,24 +4639,17 @@ static int residual_restrict(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc,
     const int w = (gf->nx + 1 + 64 * VX - 1) / (64 * VX);       // waves needed for a full row
     // blocks of <= 256 threads (fp32 rows) leave room for two per CU: cut z in two (fp32 at 1023^3: 2.78 -> 1.82 ms)
     // (rows of <= 2 waves: 1024 blocks -- 255^3 inside the 511^3 cycle 73 -> 52 us)
-    long nch = (a.nty >= 256) ? ((w <= 4) ? 2 : 1) : ((w <= 2 && sizeof(T) == 8 ? 1024 : 512) + a.nty - 1) / a.nty;
-    if (g_zchunk > 0) nch = (nkc + g_zchunk - 1) / g_zchunk;
-    else if (c->chunk_planes > 1 && nch < (nkc + c->chunk_planes / 2 - 1) / (c->chunk_planes / 2)) nch = (nkc + c->chunk_planes / 2 - 1) / (c->chunk_planes / 2);
-    int kcc = (int)((nkc + nch - 1) / nch);
-    if (kcc < 4) kcc = 4;
-    if (kcc > nkc) kcc = nkc;
-    a.kcc = kcc;
-    const long ntz = (nkc + kcc - 1) / kcc;
-    const unsigned nblk = (unsigned)(a.nty * ntz);
+    const long nch = (a.nty >= 256) ? ((w <= 4) ? 2 : 1) : ((w <= 2 && sizeof(T) == 8 ? 1024 : 512) + a.nty - 1) / a.nty;
+    // coarse planes: the chunk_planes hint (fine planes) halved
+    const Chunks ch = cut_chunks_n(c, nkc, nch, {/*min*/ 4, false, /*even*/ false, /*clamp*/ true, /*hint*/ 1, 2});
+    a.kcc = ch.len;
+    const unsigned nblk = (unsigned)(a.nty * ch.count);
     hipStream_t s = S(c, stream);
-    // register / shuffle form (k_rrrow): tuning variants 31 / 32 force it with prefetch distance 1 / 2, 30 forces the LDS-tile form
-    const int rowpd = row_shape_ok<T>(gf) ? row_form(w, sizeof(T)) : 0;
-    if (rowpd == 34 || rowpd == 35) launch_rrrow<T, 1, 2>(w, nblk, s, a);      // DPP lane shifts
-    else if (rowpd) launch_rrrow<T, 1, 0>(w, nblk, s, a);
-    else if (w <= 1) hipLaunchKernelGGL((k_resrestrict<T, 1>), dim3(nblk), dim3(64), 0, s, a);
-    else if (w <= 2) hipLaunchKernelGGL((k_resrestrict<T, 2>), dim3(nblk), dim3(128), 0, s, a);
-    else if (w <= 4) hipLaunchKernelGGL((k_resrestrict<T, 4>), dim3(nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_resrestrict<T, 8>), dim3(nblk), dim3(512), 0, s, a);
+    // register / shuffle form (k_rrrow) on row shapes; MGK_TUNE_LDS_TILE forces the LDS-tile form
+    const RowForm form = row_shape_ok<T>(gf) ? row_form() : ROW_NONE;
+    if (form == ROW_DPP || form == ROW_PRED_DPP) launch_rrrow<T, 1, 2>(w, nblk, s, a);      // DPP lane shifts
+    else if (form != ROW_NONE) launch_rrrow<T, 1, 0>(w, nblk, s, a);
+    else LAUNCH_WX(width_1248, w, (k_resrestrict<T, WX>), nblk, s, a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -4803,10 +4680,10 @@ static int residual_restrict_slab(mgk_ctx *c, const mgk_geom *gf, const mgk_geom
     if (!gf || !gc) return fail(MGK_EINVAL, "mgk_residual_restrict_slab: bad arguments");
     const T *hi = nullptr;
     if (has_hi) {
-        if (!gfar || !far || gfar->dim != 3 || gfar->nz != 2 || gfar->nx != gf->nx || gfar->ny != gf->ny || gfar->pitch != gf->pitch)
+        if (!far_geom_ok(gfar, far, gf))
             return fail(MGK_EINVAL, "mgk_residual_restrict_slab: the far-plane field must have the geometry (nx, ny, 2) of the slab");
         if (gf->nz != 2 * gc->nz) return fail(MGK_EINVAL, "mgk_residual_restrict_slab: a slab with a rank above has nzf = 2 nzc");
-        hi = far + gfar->org + 2 * gfar->plane;
+        hi = far_hi_plane(far, gfar, 1);
     }
     return residual_restrict<T>(c, gf, gc, coef, b, u, bc, nullptr, 0.0, 0.0, kcbeg, kcend, stream, hi);
 }
@@ -4939,6 +4816,9 @@ __global__ void __launch_bounds__(256) k_pj2d(const PJ2dArgs a) {
         ua = ub; ub = uc; uc = un; ur = ur2; cA = cA2; cB = cB2; b0 = bn;
     }
 }
+static bool pj2d_waves(const mgk_geom *gf) {
+    return (gf->nx >= 2047 && g_variant != MGK_TUNE_LDS_TILE) || (g_variant == MGK_TUNE_PJ2D_WAVES && gf->nx >= 3);
+}
 static int prolong_jacobi_2d_waves(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
                                    const double *b, const double *ucoarse, const double *u, double *unew, void *stream,
                                    const double *ctab = nullptr, const double *dtab = nullptr) {
@@ -4946,16 +4826,13 @@ static int prolong_jacobi_2d_waves(mgk_ctx *c, const mgk_geom *gf, const mgk_geo
     a.ctab = ctab; a.dtab = dtab;
     a.u = u + gf->org; a.b = b + gf->org; a.uc = ucoarse + gc->org; a.out = unew + gf->org;
     a.nx = gf->nx; a.ny = gf->ny; a.nxc = gc->nx; a.nyc = gc->ny; a.rs = gf->pitch; a.crs = gc->pitch;
-    if (coef) { a.a0 = coef[0]; a.a2 = coef[1]; a.a3 = coef[2]; a.a4 = coef[3]; a.a6 = coef[4]; }
+    if (coef) set_coef5(a, coef);
     a.dinv = dinv; a.scale = scale;
     a.ntx = (gc->nx + 1 + 61) / 62;                           // pairs 0 .. nxc
-    long nch = (4096 + a.ntx - 1) / a.ntx;                    // ~4096 waves (16 per CU); every chunk re-reads two fine rows
-    if (g_zchunk > 0) nch = (gf->ny + g_zchunk - 1) / g_zchunk;
-    int yc = (int)((gf->ny + nch - 1) / nch);
-    if (yc < 16 && g_zchunk <= 0) yc = 16;
-    if (yc > gf->ny) yc = gf->ny;
-    a.yc = yc;
-    const long waves = (long)a.ntx * ((gf->ny + yc - 1) / yc);
+    // ~4096 waves (16 per CU); every chunk re-reads two fine rows
+    const Chunks ch = cut_chunks(c, gf->ny, a.ntx, 4096, {/*min*/ 16, true, /*even*/ false, /*clamp*/ true, /*hint*/ 0, 0});
+    a.yc = ch.len;
+    const long waves = (long)a.ntx * ch.count;
     hipLaunchKernelGGL(k_pj2d, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
@@ -4980,36 +4857,26 @@ static int prolong_jacobi(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, co
     a.zbeg = zbeg; a.zend = zend;
     if constexpr (sizeof(T) == 8) {
         // 2-D, whole grid: independent waves from 2047^2 on (a wave marches >= 16 rows: on the small levels of the 4097^2 cycle this form
-        // takes 14-18 us where the LDS-tile kernel takes 5-8); tuning variant 30 keeps the LDS-tile kernel, 38 forces the waves
-        if (gf->dim == 2 && zbeg == 0 && zend == gf->ny && ((gf->nx >= 2047 && g_variant != 30) || (g_variant == 38 && gf->nx >= 3)))
+        // takes 14-18 us where the LDS-tile kernel takes 5-8); MGK_TUNE_LDS_TILE keeps the LDS-tile kernel, MGK_TUNE_PJ2D_WAVES forces the waves
+        if (gf->dim == 2 && zbeg == 0 && zend == gf->ny && pj2d_waves(gf))
             return prolong_jacobi_2d_waves(c, gf, gc, coef, dinv, scale, (const double *)b, (const double *)ucoarse, (const double *)u, (double *)unew, stream);
     }
     constexpr int VX = 16 / sizeof(T);
     const int w = (gf->nx + 1 + 64 * VX - 1) / (64 * VX);        // waves per full row
-    const int rowpd = row_shape_ok<T>(gf) ? row_form(w, sizeof(T)) : 0;
-    if (rowpd) {
+    const RowForm form = row_shape_ok<T>(gf) ? row_form() : ROW_NONE;
+    if (form != ROW_NONE) {
         // register / shuffle form (k_pjrow): full-row tiles of 4 rows; one 512-thread block per CU at 1023^3 (256 tiles, one
         // chunk), smaller blocks two per CU
-        PJArgs<T> q; memset(&q, 0, sizeof(q));
-        q.u = a.u; q.b = a.b; q.uc = a.uc; q.out = a.out;
-        q.nx = gf->nx; q.ny = gf->ny; q.nz = gf->nz; q.nxc = gc->nx; q.nyc = gc->ny; q.nzc = gc->nz;
-        q.rs = gf->pitch; q.ms = gf->plane; q.crs = gc->pitch; q.cms = gc->plane;
-        q.a0 = a.a0; q.a1 = a.a1; q.a2 = a.a2; q.a3 = a.a3; q.a4 = a.a4; q.a5 = a.a5; q.a6 = a.a6; q.dinv = a.dinv; q.scale = a.scale;
-        q.zbeg = zbeg; q.zend = zend;
-        q.nty = (gf->ny + 3) / 4;
+        PJArgs<T> q = pj_from_st(a, gf, zbeg, zend);
+        q.uc = a.uc; q.nxc = gc->nx; q.nyc = gc->ny; q.nzc = gc->nz; q.crs = gc->pitch; q.cms = gc->plane;
         const int nzr = zend - zbeg;
         const long target = (w > 4) ? 256 : (w <= 2 && sizeof(T) == 8 ? 1024 : 512);       // (255^3 inside the 511^3 cycle: 76 -> 67 us)
-        long nch = (q.nty >= target) ? 1 : (target + q.nty - 1) / q.nty;
-        if (g_zchunk > 0) nch = (nzr + g_zchunk - 1) / g_zchunk;
-        else if (c->chunk_planes > 0 && nch < (nzr + c->chunk_planes - 1) / c->chunk_planes) nch = (nzr + c->chunk_planes - 1) / c->chunk_planes;
-        int zc = (int)((nzr + nch - 1) / nch);
-        if (zc < 4) zc = 4;
-        if (zc > nzr) zc = nzr;
-        q.zc = zc;
-        const unsigned nblk = (unsigned)(q.nty * ((nzr + zc - 1) / zc));
-        if (rowpd == 33) launch_pjrow<T, 1, 1>(w, nblk, S(c, stream), q);          // unconditional loads
-        else if (rowpd == 34) launch_pjrow<T, 1, 3>(w, nblk, S(c, stream), q);     // + DPP lane shifts
-        else if (rowpd == 35) launch_pjrow<T, 1, 2>(w, nblk, S(c, stream), q);     // predicated loads, DPP lane shifts
+        const Chunks ch = cut_chunks(c, nzr, q.nty, target, {/*min*/ 4, false, /*even*/ false, /*clamp*/ true, /*hint*/ 1, 1});
+        q.zc = ch.len;
+        const unsigned nblk = (unsigned)(q.nty * ch.count);
+        if (form == ROW_UNCOND) launch_pjrow<T, 1, 1>(w, nblk, S(c, stream), q);          // unconditional loads
+        else if (form == ROW_DPP) launch_pjrow<T, 1, 3>(w, nblk, S(c, stream), q);     // + DPP lane shifts
+        else if (form == ROW_PRED_DPP) launch_pjrow<T, 1, 2>(w, nblk, S(c, stream), q);     // predicated loads, DPP lane shifts
         else launch_pjrow<T, 1, 0>(w, nblk, S(c, stream), q);
         HIPCHK(hipGetLastError());
         return 0;
@@ -5627,18 +5494,15 @@ static int residual_restrict_2d(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *
     RR2dArgs a; memset(&a, 0, sizeof(a));
     a.u = u + gf->org; a.b = b + gf->org; a.bc = bc + gc->org; a.uc0 = uc0 ? uc0 + gc->org : nullptr;
     a.nx = gf->nx; a.ny = gf->ny; a.nxc = gc->nx; a.nyc = gc->ny; a.rs = gf->pitch; a.crs = gc->pitch;
-    if (coef) { a.a0 = coef[0]; a.a2 = coef[1]; a.a3 = coef[2]; a.a4 = coef[3]; a.a6 = coef[4]; }
+    if (coef) set_coef5(a, coef);
     a.dinv_c = dinv_c; a.scale_c = scale_c; a.ctab = ctab; a.dtab_c = dtab_c;
     a.ntx = (gc->nx + 61) / 62;
-    long nch = (4096 + a.ntx - 1) / a.ntx;                    // ~4096 waves (16 per CU); every chunk re-reads two fine rows
-    if (g_zchunk > 0) nch = (gc->ny + g_zchunk - 1) / g_zchunk;
-    int ycc = (int)((gc->ny + nch - 1) / nch);
-    if (ycc < 4) ycc = 4;
-    if (ycc > gc->ny) ycc = gc->ny;
+    // ~4096 waves (16 per CU); every chunk re-reads two fine rows
+    int ycc = cut_chunks(c, gc->ny, a.ntx, 4096, {/*min*/ 4, false, /*even*/ false, /*clamp*/ true, /*hint*/ 0, 0}).len;
     // round 3: the levels that fit the caches (rows of <= 1024) lack waves, not bandwidth: chunks of TWO coarse rows whose seven fine rows
     // of u (and five of b) are all requested before the first residual (PD = 5: the register ring holds the whole chunk), as the short
-    // form of k_jacobi3_2d.  Tuning variants 55 / 56 force the marching / the short form.
-    const bool shortf = (g_variant == 56) || (g_variant != 55 && g_zchunk <= 0 && gf->nx + 1 <= 1024);
+    // form of k_jacobi3_2d.  MGK_TUNE_RR2D_MARCH / _SHORT force the marching / the short form.
+    const bool shortf = (g_variant == MGK_TUNE_RR2D_SHORT) || (g_variant != MGK_TUNE_RR2D_MARCH && g_zchunk <= 0 && gf->nx + 1 <= 1024);
     if (shortf) ycc = gc->ny < 2 ? gc->ny : 2;
     a.ycc = ycc;
     const long waves = (long)a.ntx * ((gc->ny + ycc - 1) / ycc);
@@ -5779,17 +5643,14 @@ static int sweep_residual_restrict_2d(mgk_ctx *c, const mgk_geom *gf, const mgk_
     SRR2dArgs a; memset(&a, 0, sizeof(a));
     a.u = u + gf->org; a.b = b + gf->org; a.out = unew + gf->org; a.bc = bc + gc->org; a.uc0 = uc0 ? uc0 + gc->org : nullptr;
     a.nx = gf->nx; a.ny = gf->ny; a.nxc = gc->nx; a.nyc = gc->ny; a.rs = gf->pitch; a.crs = gc->pitch;
-    if (coef) { a.a0 = coef[0]; a.a2 = coef[1]; a.a3 = coef[2]; a.a4 = coef[3]; a.a6 = coef[4]; }
+    if (coef) set_coef5(a, coef);
     a.dinv = dinv; a.scale = scale; a.dinv_c = dinv_c; a.scale_c = scale_c;
     a.ctab = ctab; a.dtab = dtab; a.dtab_c = dtab_c;
     a.ntx = (gc->nx + 1 + 60) / 61;                           // pairs 0 .. nxc (the last one holds the last fine column and the ghost column)
-    long nch = (4096 + a.ntx - 1) / a.ntx;                    // ~4096 waves (16 per CU); every chunk re-reads four fine rows
-    if (g_zchunk > 0) nch = (gc->ny + g_zchunk - 1) / g_zchunk;
-    int ycc = (int)((gc->ny + nch - 1) / nch);
-    if (ycc < 8 && g_zchunk <= 0) ycc = 8;
-    if (ycc > gc->ny) ycc = gc->ny;
-    a.ycc = ycc;
-    const long waves = (long)a.ntx * ((gc->ny + ycc - 1) / ycc);
+    // ~4096 waves (16 per CU); every chunk re-reads four fine rows
+    const Chunks ch = cut_chunks(c, gc->ny, a.ntx, 4096, {/*min*/ 8, true, /*even*/ false, /*clamp*/ true, /*hint*/ 0, 0});
+    a.ycc = ch.len;
+    const long waves = (long)a.ntx * ch.count;
     hipLaunchKernelGGL(k_srr2d, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
@@ -5868,7 +5729,7 @@ extern "C" int mgk_prolong_jacobi_rowcoef_f64(mgk_ctx *c, const mgk_geom *gf, co
     XferArgs x;
     int rc = xfer_args(gf, gc, x);
     if (rc) return rc;
-    if ((gf->nx >= 2047 && g_variant != 30) || (g_variant == 38 && gf->nx >= 3))          // independent waves, as mgk_prolong_jacobi_f64 in 2-D
+    if (pj2d_waves(gf))                    // independent waves, as mgk_prolong_jacobi_f64 in 2-D
         return prolong_jacobi_2d_waves(c, gf, gc, nullptr, 1.0, scale, b, uc, u, unew, stream, ctab, dtab);
     StArgs<double> a; memset(&a, 0, sizeof(a));
     a.u = u + gf->org; a.b = b + gf->org; a.out = unew + gf->org;

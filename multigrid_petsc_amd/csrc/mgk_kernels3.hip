@@ -272,22 +272,18 @@ static int jacobi3_2d(mgk_ctx *c, const mgk_geom *g, const mgk_geom *gc, const d
         if (!gc || !uc || gc->dim != 2 || g->nx != 2 * gc->nx + 1 || g->ny != 2 * gc->ny + 1) return fail(MGK_EINVAL, "mgk_prolong_jacobi3_2d: coarse grid does not match");
         a.uc = uc + gc->org; a.nxc = gc->nx; a.nyc = gc->ny; a.crs = gc->pitch;
     }
-    if (coef) { a.a0 = coef[0]; a.a2 = coef[1]; a.a3 = coef[2]; a.a4 = coef[3]; a.a6 = coef[4]; }
+    if (coef) set_coef5(a, coef);
     a.dinv = dinv; a.scale = CHEB ? cheb[0] : scale; a.ctab = ctab; a.dtab = dtab;
     if (CHEB) for (int q = 0; q < 6; q++) a.ch[q] = cheb[1 + q];
     if (rout) { if (!NORM || rout == unew || rout == u || rout == b) return fail(MGK_EINVAL, "mgk_jacobi3_2d_sumsq_store_f64: bad arguments"); a.rout = rout + g->org; }
     a.ntx = ((g->nx + 1) / 2 + 59) / 60;                      // pairs 0 .. (nx-1)/2
     // levels that fit the caches (rows of <= 1024): short chunks with every load up front (they lack waves, not bandwidth); the big
     // levels: ~4096 waves (16 per CU) marching over long chunks -- a chunk pays four warm-up steps (two sweep-equivalents) and re-reads
-    // six rows.  Tuning variants 50 / 51 / 52 force the marching form / chunks of 4 / chunks of 8 rows.
+    // six rows.  MGK_TUNE_J3_2D_MARCH / _CHUNK4 / _CHUNK8 force the marching form / chunks of 4 / chunks of 8 rows.
     int ycs = (g->nx + 1 <= 1024) ? 4 : 0;
-    if (g_variant == 50) ycs = 0; else if (g_variant == 51) ycs = 4; else if (g_variant == 52) ycs = 8;
-    if (g_zchunk > 0 && g_variant != 51 && g_variant != 52) ycs = 0;      // an explicit chunk length: the marching form
-    long nch = (4096 + a.ntx - 1) / a.ntx;
-    if (g_zchunk > 0) nch = (g->ny + g_zchunk - 1) / g_zchunk;
-    int yc = (int)((g->ny + nch - 1) / nch);
-    if (yc < 12 && g_zchunk <= 0) yc = 12;
-    if (yc > g->ny) yc = g->ny;
+    if (g_variant == MGK_TUNE_J3_2D_MARCH) ycs = 0; else if (g_variant == MGK_TUNE_J3_2D_CHUNK4) ycs = 4; else if (g_variant == MGK_TUNE_J3_2D_CHUNK8) ycs = 8;
+    if (g_zchunk > 0 && g_variant != MGK_TUNE_J3_2D_CHUNK4 && g_variant != MGK_TUNE_J3_2D_CHUNK8) ycs = 0;      // an explicit chunk length: the marching form
+    int yc = cut_chunks(c, g->ny, a.ntx, 4096, {/*min*/ 12, true, /*even*/ false, /*clamp*/ true, /*hint*/ 0, 0}).len;
     if (ycs) yc = ycs;
     long waves = (long)a.ntx * ((g->ny + yc - 1) / yc);
     if (NORM && ((waves + 3) / 4 + 7) * 4 > c->max_partials) {    // one partial per wave: longer chunks where that would overflow the slots
@@ -300,14 +296,14 @@ static int jacobi3_2d(mgk_ctx *c, const mgk_geom *g, const mgk_geom *gc, const d
     a.yc = yc;
     unsigned nblk = (unsigned)((waves + 3) / 4);
     // XCD-aware tile order where it paid (MI355X, HIP events): the short-chunk form (1023^2: 10.5 -> 9.3 us) and the marching form from
-    // 4095^2 on (69 -> 66 us); at 2047^2 the dispatch order was quicker (23.6 against 25.3 us).  53 / 54 force dispatch / XCD order
-    a.xcd = (g_variant == 54) || (g_variant != 53 && nblk >= 64 && (ycs != 0 || g->nx >= 4095));
+    // 4095^2 on (69 -> 66 us); at 2047^2 the dispatch order was quicker (23.6 against 25.3 us).  MGK_TUNE_DISPATCH_ORDER / _XCD_ORDER force either
+    a.xcd = (g_variant == MGK_TUNE_XCD_ORDER) || (g_variant != MGK_TUNE_DISPATCH_ORDER && nblk >= 64 && (ycs != 0 || g->nx >= 4095));
     if (a.xcd) nblk = (nblk + 7u) & ~7u;
     a.nwaves = (int)waves;
-    // odd chunks marched downwards (tuning variant 58 only: bit-identical, but at 4095^2 it measured 67-68 us against 64 us with every chunk
+    // odd chunks marched downwards (MGK_TUNE_J3_2D_ODD_DOWN only: bit-identical, but at 4095^2 it measured 67-68 us against 64 us with every chunk
     // marching upwards -- the shared rows are served by the Infinity Cache either way)
-    a.bous = (ycs == 0 && g_variant == 58) ? 1 : (ycs == 0 && g_variant == 59) ? 2 : 0;      // 59: EVERY chunk downwards
-    a.plainst = (g_variant == 60) ? 1 : (g_variant == 61) ? 2 : 0;      // tuning: 60 forces ordinary stores, 61 non-temporal ones; default by field size
+    a.bous = (ycs != 0) ? 0 : (g_variant == MGK_TUNE_J3_2D_ODD_DOWN) ? 1 : (g_variant == MGK_TUNE_J3_2D_ALL_DOWN) ? 2 : 0;
+    a.plainst = (g_variant == MGK_TUNE_J3_2D_STORE_PLAIN) ? 1 : (g_variant == MGK_TUNE_J3_2D_STORE_NT) ? 2 : 0;      // default: by field size
     if (NORM) {
         if (!norm_parts || 4L * nblk > c->max_partials) return fail(MGK_EINVAL, "mgk_jacobi3_2d_sumsq_f64: more waves than partial slots");
         a.partials = c->partials;
@@ -578,7 +574,7 @@ static int jacobi3_3d_launch(mgk_ctx *c, J33Args &a, const mgk_geom *g, int *nor
     a.nty = (g->ny + TY - 1) / TY;
     // one wave per SIMD: 1024 run at a time; cut z so that the wave tiles are a whole number of rounds (>= 4), chunks of >= 32 planes
     const long per = (long)a.ntx * a.nty;
-    int ntz = 1;
+    int ntz = 1;                                              // (open-coded, not cut_chunks: the count grows while the chunks stay >= 32 planes)
     if (g_zchunk > 0) ntz = (g->nz + g_zchunk - 1) / g_zchunk;
     else { while (per * ntz < 4096 && g->nz / (ntz + 1) >= 32) ntz++; }
     if (NORM) while (ntz > 1 && per * ntz + 32 > c->max_partials) ntz--;      // one partial per wave
@@ -586,14 +582,14 @@ static int jacobi3_3d_launch(mgk_ctx *c, J33Args &a, const mgk_geom *g, int *nor
     a.ntz = (g->nz + a.zc - 1) / a.zc;
     const long waves = per * a.ntz;
     unsigned nblk = (unsigned)((waves + 3) / 4);
-    a.xcd = (g_variant != 53 && nblk >= 64) ? 1 : 0;
+    a.xcd = (g_variant != MGK_TUNE_DISPATCH_ORDER && nblk >= 64) ? 1 : 0;
     if (a.xcd) nblk = (nblk + 7u) & ~7u;
     if (NORM) {
         if (!norm_parts || 4L * nblk > c->max_partials) return fail(MGK_EINVAL, "mgk_jacobi3_sumsq_f64: more waves than partial slots");
         a.partials = c->partials;
         *norm_parts = (int)(4 * nblk);
     }
-    if (g_variant == 64) hipLaunchKernelGGL((k_jacobi3_3d<TY, NORM, 0>), dim3(nblk), dim3(256), 0, S(c, stream), a);      // row by row (64)
+    if (g_variant == MGK_TUNE_J3_3D_ROWWISE) hipLaunchKernelGGL((k_jacobi3_3d<TY, NORM, 0>), dim3(nblk), dim3(256), 0, S(c, stream), a);      // row by row
     else hipLaunchKernelGGL((k_jacobi3_3d<TY, NORM, 1>), dim3(nblk), dim3(256), 0, S(c, stream), a);                       // term by term over the rows
     HIPCHK(hipGetLastError());
     return 0;
@@ -605,11 +601,11 @@ static int jacobi3_3d(mgk_ctx *c, const mgk_geom *g, const double *coef, double 
     J33Args a; memset(&a, 0, sizeof(a));
     a.u = u + g->org; a.b = b + g->org; a.out = unew + g->org;
     a.nx = g->nx; a.ny = g->ny; a.nz = g->nz; a.rs = g->pitch; a.ms = g->plane;
-    a.a0 = coef[0]; a.a1 = coef[1]; a.a2 = coef[2]; a.a3 = coef[3]; a.a4 = coef[4]; a.a5 = coef[5]; a.a6 = coef[6];
+    set_coef7(a, coef);
     a.dinv = dinv; a.scale = scale;
     // rows per wave tile: 4 (480-498 registers per lane, none in scratch); with the norm 3 (456): the 4-row form would spill 28-38 registers
-    // to scratch.  Tuning variants 62 / 63 force 2 / 3 rows
-    const int ty = (g_variant == 62) ? 2 : (g_variant == 63 || NORM) ? 3 : 4;
+    // to scratch.  MGK_TUNE_J3_3D_TY2 / _TY3 force 2 / 3 rows
+    const int ty = (g_variant == MGK_TUNE_J3_3D_TY2) ? 2 : (g_variant == MGK_TUNE_J3_3D_TY3 || NORM) ? 3 : 4;
     if (ty == 2) return jacobi3_3d_launch<2, NORM>(c, a, g, norm_parts, stream);
     if (ty == 3) return jacobi3_3d_launch<3, NORM>(c, a, g, norm_parts, stream);
     return jacobi3_3d_launch<4, NORM>(c, a, g, norm_parts, stream);

@@ -161,7 +161,7 @@ int kry_args(KryArgs &a, const mgk_geom *g, int k, const double *const *v) {
     memset(&a, 0, sizeof(a));
     a.nx = g->nx; a.ny = g->ny; a.npairs = (g->nx + 1) / 2; a.k = k;
     a.pitch = g->pitch; a.plane = g->plane; a.nrows = (long)g->ny * g->nz;
-    a.nt = g_variant == 0 ? 0 : g_variant == 1 ? 1 : -1;
+    a.nt = store_policy();
     for (int i = 0; i < MGK_KRYLOV_MAX; i++) {
         if (i < k && !v[i]) return 1;
         a.v[i] = i < k ? v[i] + g->org : nullptr;

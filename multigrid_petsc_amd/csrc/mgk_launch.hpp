@@ -1,0 +1,67 @@
+// mgk_launch.hpp -- the launch rules of libmgk.so's host side, each stated once (included by mgk_dev.hpp, after mgk_ctx and the tuning knobs):
+// wave width -> kernel instantiation, the cut of the marching axis into chunks, the far-plane fields of the slab launches, the stencil
+// coefficients of the argument structs.  Host code only: nothing in here changes what a kernel computes.
+#pragma once
+#include <type_traits>
+
+// ---- wave width: the runtime number of waves per row `w` picks the compile-time WX among WXS (ascending): the first one with w <= WX, the
+// last one for anything wider.  f is called with std::integral_constant<int, WX>.  The instantiations are those of the listed widths only.
+template <int W0, int... WS, typename F>
+static inline void with_width(int w, F &&f) {
+    if constexpr (sizeof...(WS) == 0) f(std::integral_constant<int, W0>{});
+    else if (w <= W0) f(std::integral_constant<int, W0>{});
+    else with_width<WS...>(w, f);
+}
+template <typename F> static inline void width_1248(int w, F &&f) { with_width<1, 2, 4, 8>(w, f); }
+template <typename F> static inline void width_48(int w, F &&f) { with_width<4, 8>(w, f); }      // the pj2 kernels: rows of 512 / 1024 only
+// LAUNCH_WX(width_1248, w, (k_foo<T, WX, 3>), nblk, stream, args...): blocks of 64 * WX threads; `kernel` names WX
+#define LAUNCH_WX(pick, w, kernel, nblk, s, ...)                                                      \
+    pick(w, [&](auto wx_) {                                                                           \
+        constexpr int WX = decltype(wx_)::value;                                                      \
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(nblk)), dim3(64 * WX), 0, s, __VA_ARGS__);         \
+    })
+
+// ---- chunks of the marching axis.  `extent` planes (rows) are cut into `nch` chunks -- by default as many as bring `tiles` tiles to
+// `target` blocks -- unless the knob g_zchunk gives the chunk length; a slab context's chunk_planes hint may ask for more, shorter chunks.
+struct ChunkRule {
+    int min_len;            // shortest chunk the site takes
+    bool zchunk_below_min;  // an explicit g_zchunk may go below min_len
+    bool even;              // length rounded up to an even number (every chunk starts on an even plane)
+    bool clamp;             // never longer than the extent
+    int hint_mul, hint_div; // chunk_planes hint: at least ceil(hint_mul * extent / (chunk_planes / hint_div)) chunks; hint_div 0: hint not read
+};
+struct Chunks { int len; long count; };
+static inline Chunks cut_chunks_n(const mgk_ctx *c, int extent, long nch, const ChunkRule &r) {
+    if (g_zchunk > 0) nch = (extent + g_zchunk - 1) / g_zchunk;
+    else if (r.hint_div && c->chunk_planes / r.hint_div > 0) {
+        const int cp = c->chunk_planes / r.hint_div;
+        if (nch < (r.hint_mul * extent + cp - 1) / cp) nch = (r.hint_mul * extent + cp - 1) / cp;
+    }
+    int len = (int)((extent + nch - 1) / nch);
+    if (r.even) len = (len + 1) & ~1;
+    if (len < r.min_len && !(r.zchunk_below_min && g_zchunk > 0)) len = r.min_len;
+    if (r.clamp && len > extent) len = extent;
+    return {len, (long)((extent + len - 1) / len)};
+}
+static inline Chunks cut_chunks(const mgk_ctx *c, int extent, long tiles, long target, const ChunkRule &r) {
+    return cut_chunks_n(c, extent, (tiles >= target) ? 1 : (target + tiles - 1) / tiles, r);
+}
+
+// ---- the far-plane field of a slab launch: geometry gfar = (nx, ny, 2) of the slab g, same pitch; its lo ghost plane holds what the rank
+// below sent (the plane below the slab's own lo ghost), its hi ghost plane what the rank above sent
+static inline bool far_geom_ok(const mgk_geom *gfar, const void *far, const mgk_geom *g) {
+    return gfar && far && gfar->dim == 3 && gfar->nz == 2 && gfar->nx == g->nx && gfar->ny == g->ny && gfar->pitch == g->pitch;
+}
+template <typename T> static inline const T *far_lo_plane(const T *far, const mgk_geom *gfar, int has) { return has ? far + gfar->org - gfar->plane : nullptr; }
+template <typename T> static inline const T *far_hi_plane(const T *far, const mgk_geom *gfar, int has) { return has ? far + gfar->org + 2 * gfar->plane : nullptr; }
+
+// ---- stencil coefficients of an argument struct with a0 .. a6, in the struct's element type: 3-D {k-1, i-1, j-1, C, j+1, i+1, k+1},
+// 2-D {i-1, j-1, C, j+1, i+1} in the slots of the same neighbours (a1, a5 stay as they are: zero)
+template <typename A> static inline void set_coef7(A &a, const double *coef) {
+    typedef decltype(a.a0) T;
+    a.a0 = (T)coef[0]; a.a1 = (T)coef[1]; a.a2 = (T)coef[2]; a.a3 = (T)coef[3]; a.a4 = (T)coef[4]; a.a5 = (T)coef[5]; a.a6 = (T)coef[6];
+}
+template <typename A> static inline void set_coef5(A &a, const double *coef) {
+    typedef decltype(a.a0) T;
+    a.a0 = (T)coef[0]; a.a2 = (T)coef[1]; a.a3 = (T)coef[2]; a.a4 = (T)coef[3]; a.a6 = (T)coef[4];
+}

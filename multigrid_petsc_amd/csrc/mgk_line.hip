@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(64) k_line_backward(const LineArgs a) {
 
 bool line_geom_ok(const mgk_geom *g) { return g && g->dim == 2 && g->nz == 1 && g->nx >= 1 && g->ny >= 1 && g->pitch <= LINE_MAX_PITCH; }
 int line_depth() { return g_zchunk >= 32 ? 32 : g_zchunk >= 16 ? 16 : g_zchunk > 0 ? 8 : 16; }
-int line_policy() { return g_variant == 0 ? 0 : g_variant == 1 ? 1 : -1; }
+int line_policy() { return store_policy(); }
 
 }  // namespace
 

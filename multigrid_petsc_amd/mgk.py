@@ -1,5 +1,7 @@
 """ctypes binding of include/mgk.h (kernel-level C ABI).  Test/bench plumbing only."""
+import contextlib
 import ctypes as C
+import enum
 import numpy as np
 from ._lib import load_mgk
 
@@ -13,6 +15,55 @@ class Geom(C.Structure):
 
 class MgkError(RuntimeError):
     pass
+
+
+class Tune(enum.IntEnum):
+    """enum mgk_tune of include/mgk.h (tests/test_abi.py holds the two together): the named values of mgk_set_tuning's first argument.
+    Values below 30 that are tile-table indices or the ring / register choice of jacobi2 stay plain integers (the table in the header)."""
+    DEFAULT = -1
+    STORE_PLAIN = 0
+    STORE_NT = 1
+    LDS_TILE = 30
+    ROW = 31
+    ROW_PD2 = 32
+    ROW_UNCOND = 33
+    ROW_DPP = 34
+    ROW_PRED_DPP = 35
+    J2_REG_PRED = 36
+    J2_RING_PRED = 37
+    PJ2D_WAVES = 38
+    J2_RING_OLD = 39
+    SRR_TY2 = 40
+    SRR_TY4 = 41
+    J2_ZERO_RINGB = 45
+    PJ2_COPY = 46
+    J3_2D_MARCH = 50
+    J3_2D_CHUNK4 = 51
+    J3_2D_CHUNK8 = 52
+    DISPATCH_ORDER = 53
+    XCD_ORDER = 54
+    RR2D_MARCH = 55
+    RR2D_SHORT = 56
+    RESERVED_57 = 57
+    J3_2D_ODD_DOWN = 58
+    J3_2D_ALL_DOWN = 59
+    J3_2D_STORE_PLAIN = 60
+    J3_2D_STORE_NT = 61
+    J3_3D_TY2 = 62
+    J3_3D_TY3 = 63
+    J3_3D_ROWWISE = 64
+
+
+@contextlib.contextmanager
+def tuning(variant=-1, zchunk=-1):
+    """set the calling thread's tuning knobs for the body and put (-1, -1) back on the way out, exceptions included"""
+    L = load_mgk()
+    L.mgk_set_tuning.restype, L.mgk_set_tuning.argtypes = None, [C.c_int, C.c_int]
+    L.mgk_set_tuning(int(variant), int(zchunk))
+    try:
+        yield
+    finally:
+        L.mgk_set_tuning(-1, -1)
 
 
 def _sigs(L):

@@ -257,6 +257,25 @@ def test_fuse_bit_names_of_the_header_and_of_the_python_mirror(tmp_path):
     assert not header["DEFAULT"] & (64 | FUSE_BITS["RES_RESTRICT_SMALL"])          # (64 is unassigned, bit 7 is for tests)
 
 
+def test_tuning_names_of_the_header_and_of_the_python_mirror(tmp_path):
+    """every MGK_TUNE_* enumerator of include/mgk.h, as a C compiler evaluates it, equals the member of multigrid_petsc_amd.Tune of that name
+    (aliases included); the forms from 30 up are distinct values, and 57 stays reserved"""
+    import subprocess
+    from multigrid_petsc_amd import Tune
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mgk.h")).read(), flags=re.S)
+    names = re.findall(r"\bMGK_TUNE_([A-Z0-9_]+)\s*=", re.search(r"enum mgk_tune \{(.*?)\}", txt, flags=re.S).group(1))
+    assert len(names) == len(set(names)) and len(names) >= 30
+    (tmp_path / "tune.c").write_text('#include <stdio.h>\n#include "mgk.h"\nint main(void) {\n'
+                                     + "".join(f'    printf("{n} %d\\n", (int)MGK_TUNE_{n});\n' for n in names) + "    return 0;\n}\n")
+    _cc(["gcc", "-std=c99", "-I" + os.path.join(ROOT, "include"), str(tmp_path / "tune.c"), "-o", str(tmp_path / "tune")])
+    out = subprocess.run([str(tmp_path / "tune")], check=True, stdout=subprocess.PIPE, text=True).stdout
+    header = {l.split()[0]: int(l.split()[1]) for l in out.splitlines()}
+    assert header == {n: int(m) for n, m in Tune.__members__.items()}
+    forms = [v for v in header.values() if v >= 30]
+    assert len(forms) == len(set(forms)) and header["DEFAULT"] == -1 and header["RESERVED_57"] == 57
+    assert (header["STORE_PLAIN"], header["STORE_NT"]) == (0, 1)
+
+
 def test_fuse_default_by_name_runs_the_cycle_of_minus_one(tmp_path):
     """the own driver over tests/mock_mgk.cpp (csrc/mg_solver.c + mg_comm.c, as tests/test_host_sanitized.py links it), 2-D npts 33, 4 levels,
     two cycles: -mg_fuse <Fuse.DEFAULT> and -mg_fuse -1 take the same passes and leave the same residual history and the same field, digit for

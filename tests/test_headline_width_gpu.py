@@ -135,10 +135,13 @@ def test_sweeps_and_norms_against_the_oracle(mgk, orc, n, nz):
         assert _close(ss.value, orc.sumsq(r1))
         assert t.ghosts_clean(o)
         if L.mgk_jacobi2_zero_ok_f64(g) == 1:
-            o = t.out()
-            mgk._chk(L.mgk_jacobi2_zero_f64(mgk.ctx, g, t.coef, t.dinv, SCALE, t.db, o, None))
             z3 = t.J(t.J(t.J(np.zeros_like(t.u), zero_guess=True)))
-            assert np.array_equal(t.get(o), z3), f"mgk_jacobi2_zero_f64 zc={zc}"
+            for var in (-1, 45):                                    # k_jacobi2<double,8|4,3,true> (default) and the ring form k_jacobi2b<double,8|4,true>
+                L.mgk_set_tuning(var, zc)
+                o = t.out()
+                mgk._chk(L.mgk_jacobi2_zero_f64(mgk.ctx, g, t.coef, t.dinv, SCALE, t.db, o, None))
+                assert np.array_equal(t.get(o), z3), f"mgk_jacobi2_zero_f64 variant={var} zc={zc}"
+            L.mgk_set_tuning(-1, zc)
         o = t.out()
         mgk._chk(L.mgk_jacobi_zero_f64(mgk.ctx, g, t.dinv, SCALE, t.db, o, None))
         assert np.array_equal(t.get(o), t.J(np.zeros_like(t.u), zero_guess=True))

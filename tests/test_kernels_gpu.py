@@ -194,7 +194,7 @@ def test_fused_residual_restrict_bit_exact(mgk, orc, nf):
     gf, gc = mgk.geom(3, nf), mgk.geom(3, nc)
     du, db, dbc = mgk.to_field(gf, u), mgk.to_field(gf, b), mgk.field(gc)
     want = orc.restrict(3, nf, orc.residual(3, nf, As, b, u))
-    for variant in (30, 31, 34):            # LDS-tile form, register / shuffle form (ds_bpermute / DPP lane shifts)
+    for variant in (30, 31, 32, 34):        # LDS-tile form, register / shuffle form (ds_bpermute / DPP lane shifts)
         for zc in (-1, 5):
             mgk.L.mgk_set_tuning(variant, zc)
             mgk._chk(mgk.L.mgk_memset0(mgk.ctx, dbc, 8 * gc.total, None))
@@ -852,11 +852,11 @@ def test_three_sweeps_from_the_zero_guess_in_one_pass(mgk, orc, n, prec):
         mgk._chk(mgk.L.mgk_jacobi2_f64(mgk.ctx, C.byref(g), mgk.coef(As), dinv, 0.8, db, d1, d2, None))
         want = mgk.raw_field(g, d2)
         assert np.array_equal(mgk.from_field(g, d2), orc.jacobi(3, n, As, 0.8, b, orc.jacobi(3, n, As, 0.8, b, orc.jacobi(3, n, As, 0.8, b, np.zeros(n ** 3), zero_guess=True))))
-        for zc in (-1, 8, 21):
-            mgk.L.mgk_set_tuning(-1, zc)
+        for var, zc in ((-1, -1), (-1, 8), (-1, 21), (45, -1), (45, 8)):      # 45: the ring form k_jacobi2b, which fp64 does not take by default
+            mgk.L.mgk_set_tuning(var, zc)
             mgk._chk(mgk.L.mgk_memset0(mgk.ctx, dout, 8 * g.total, None))
             mgk._chk(mgk.L.mgk_jacobi2_zero_f64(mgk.ctx, C.byref(g), mgk.coef(As), dinv, 0.8, db, dout, None))
-            assert np.array_equal(mgk.raw_field(g, dout), want), f"zc={zc}"
+            assert np.array_equal(mgk.raw_field(g, dout), want), f"variant={var} zc={zc}"
         esz = 8
     else:
         g = mgk.geom32(n)

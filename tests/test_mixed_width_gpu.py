@@ -248,7 +248,7 @@ def test_transfers_at_width(mgk, orc, nx, ny, nz):
     bcu = t.R(t.u)
     jzc = t.Jc0(bc)
     assert np.abs(bc).max() > 0 and np.abs(jzc).max() > 0
-    for v in (-1, 30, 31, 33, 35):
+    for v in (-1, 30, 31, 32, 33, 35):
         for zc in (-1, 5):
             L.mgk_set_tuning(v, zc)
             o = t.out()

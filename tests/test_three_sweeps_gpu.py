@@ -40,7 +40,8 @@ def test_three_sweeps_2d_bit_exact(mgk, orc, n):
     L, coef = mgk.L, mgk.coef(As)
     # default choice; the marching form (50) and the short-chunk forms (51: 4 rows, 52: 8 rows) forced; chunk seams everywhere
     # (tuning variants: 58 marches the odd chunks downwards, 59 every chunk; neither is a default)
-    for var, zc in ((-1, -1), (50, -1), (51, -1), (52, -1), (-1, 1), (-1, 5), (-1, 12), (-1, 64), (58, -1), (58, 5), (58, 12), (57, -1), (59, -1), (59, 5)):
+    for var, zc in ((-1, -1), (50, -1), (51, -1), (52, -1), (-1, 1), (-1, 5), (-1, 12), (-1, 64), (58, -1), (58, 5), (58, 12), (57, -1), (59, -1), (59, 5),
+                    (53, -1), (54, -1), (54, 5), (60, -1), (61, -1)):      # dispatch / XCD tile order, ordinary / non-temporal stores
         L.mgk_set_tuning(var, zc)
         mgk._chk(L.mgk_memset0(mgk.ctx, dout, 8 * g.total, None))
         mgk._chk(L.mgk_jacobi3_2d_f64(mgk.ctx, C.byref(g), coef, dinv, 0.8, None, None, db, du, dout, None))
