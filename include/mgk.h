@@ -566,6 +566,26 @@ int  mgk_line_forward_f64(mgk_ctx *ctx, const mgk_geom *g, const double *atab, c
 int  mgk_line_backward_f64(mgk_ctx *ctx, const mgk_geom *g, const double *qtab, double scale, const double *z, const double *u,
                            double *unew, void *stream);
 
+/* ---- x-line Jacobi on the 2-D row-table operators (csrc/mg_xline.c; kernels in csrc/mgk_xline.hip) ----
+ * One sweep u <- u + scale T_x^-1 (b - A u), T_x = the x-tridiagonal part of A, in two passes.  In grid row i T_x is the constant-band matrix
+ * (W_i, C_i, E_i), {S, W, C, E, N}_i = atab[5 i + 0..4]; its factorisation along the columns j is ONE device table, in C99 double without FMA
+ *   m_{i,0} = C_i, g_{i,0} = 1/m_{i,0};  j >= 1: l_{i,j} = W_i g_{i,j-1}, m_{i,j} = C_i - l_{i,j} E_i, g_{i,j} = 1/m_{i,j}
+ * gtab[i gstride + j] = g_{i,j}; gstride == 0: one row of nx doubles serves every grid row (the uniform mesh); otherwise gstride >= nx (a
+ * multiple of 16 on a 128-byte aligned table keeps the loads line-wide).  The multipliers l_{i,j} = W_i g_{i,j-1} (l_{i,0} = 0) and
+ * q_{i,j} = E_i g_{i,j} are one rounded product each, formed by the kernels; atab is needed by both passes.
+ *   mgk_xline_forward_f64    r = b - A u (the five terms in the order of mgk_rowcoef_f64 mode 1); y_{i,0} = r_{i,0}, y_{i,j} = r_{i,j} - l_{i,j} y_{i,j-1};
+ *                            z_{i,j} = y_{i,j} g_{i,j}.  u == NULL: the zero guess, r = b.  z must not alias b or u.       32 (24) B per unknown
+ *   mgk_xline_backward_f64   e_{i,n-1} = z_{i,n-1}, e_{i,j} = z_{i,j} - q_{i,j} e_{i,j+1};  unew = u + scale e; u == NULL: the zero guess, unew = scale e.
+ *                            unew may be u itself: a sweep swaps no buffers.                                            32 (24) B per unknown
+ * (with gstride == 0 the table stays in cache: 24 (16) and 24 (16).)  Multiply and subtract are rounded separately; nothing outside the interior
+ * of an output is written, and neither the ghost ring nor the padding of an input is read.  The pitch and gstride may be at most 2^21 doubles
+ * (MGK_EINVAL beyond).  Stores and knobs as the y-line passes; the second argument of mgk_set_tuning, > 0, is the depth of the prefetch ring
+ * in tiles of 16 columns (rounded down to a built one: 1, 2, 3; default 1). */
+int  mgk_xline_forward_f64(mgk_ctx *ctx, const mgk_geom *g, const double *atab, const double *gtab, long gstride,
+                           const double *b, const double *u, double *z, void *stream);
+int  mgk_xline_backward_f64(mgk_ctx *ctx, const mgk_geom *g, const double *atab, const double *gtab, long gstride, double scale,
+                            const double *z, const double *u, double *unew, void *stream);
+
 /* Named values of mgk_set_tuning's first argument.  From 30 up a value selects ONE form of ONE launcher (every other launcher takes it as
  * "no special form"); the values below 30 are read three ways, see the table under the enum.  MGK_TUNE_STORE_* name the 0 / 1 reading of
  * the Krylov and line passes.  mgk_set_tuning takes any int: a value nothing reads selects nothing. */

@@ -20,7 +20,7 @@ extern "C" {
 
 typedef enum { MG_KSP_RICHARDSON = 0, MG_KSP_CHEBYSHEV = 1 } mg_ksp_type;
 typedef enum { MG_PREC_FP64 = 0, MG_PREC_MIXED = 1 } mg_precision;
-typedef enum { MG_PC_JACOBI = 0, MG_PC_LINE_Y = 1 } mg_pc_type;
+typedef enum { MG_PC_JACOBI = 0, MG_PC_LINE_Y = 1, MG_PC_LINE_X = 2, MG_PC_LINE_ALT = 3 } mg_pc_type;
 
 /* the bits of mg_config.fuse: one fused pass (or family of passes) each.  The VALUES are ABI: tests, bench.py, the tools and
  * `mgpoisson -mg_fuse N` pass numerals.  "(bit N)" is the name the bit goes by in DESIGN.md, the tests and the profiles. */
@@ -113,7 +113,13 @@ typedef struct mg_config {
                          * the cycle count no longer grows with npts.  2-D, fp64, one rank, Richardson, meshes 0 / 1 / 2, any v and scale;
                          * anything else is refused by mg_solver_create with MGK_EINVAL, and so are mg_solver_fmg*, mg_solver_solve_gmres on
                          * such a solver.  The fuse bits that bake point Jacobi into a pass (1, 3, 5, 8-15) are cleared; bits 0 and 2 stay,
-                         * the coarse levels run by launch inside the HIP graph (a line sweep swaps no buffers) */
+                         * the coarse levels run by launch inside the HIP graph (a line sweep swaps no buffers).
+                         * MG_PC_LINE_X (2) x-line Jacobi: the same with T the x-tridiagonal part of A, solved exactly in every row (one table
+                         * per level; mgk_xline_forward_f64 / mgk_xline_backward_f64), for a mesh stretched in x.  MG_PC_LINE_ALT (3) alternating
+                         * line relaxation: within one smoothing (one KSPSolve of max_it sweeps, counted from 0 in every call) sweep k is a
+                         * y-line sweep for even k and an x-line sweep for odd k -- the same number of sweeps as MG_PC_LINE_Y, and a cycle count
+                         * independent of npts on meshes 0, 1 and 2.  Both under the conditions of MG_PC_LINE_Y, with
+                         * the same refusals */
 } mg_config;
 
 void mg_config_default(mg_config *cfg);     /* poisson.in defaults + -pc_type jacobi -ksp_richardson_scale 1 */

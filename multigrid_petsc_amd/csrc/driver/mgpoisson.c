@@ -85,7 +85,11 @@ int main(int argc, char **argv) {
     if ((v = get("-mg_pair_min_n"))) c.pair_min_n = atoi(v);
     if ((v = get("-mg_graph"))) c.graph = atoi(v);
     if ((v = get("-pc_type")) && !strcmp(v, "yline")) c.pc_type = MG_PC_LINE_Y;     /* y-line Jacobi (2-D; the remedy for -mesh 1) */
-    else if (v && strcmp(v, "jacobi")) { fprintf(stderr, "mgpoisson: only -pc_type jacobi and -pc_type yline are built\n"); return 2; }
+    else if (v && !strcmp(v, "altline")) c.pc_type = MG_PC_LINE_ALT;                /* y- and x-line sweeps in turn (2-D; -mesh 0, 1 and 2 alike) */
+    else if (v && strcmp(v, "jacobi")) {                                            /* (x-line Jacobi alone, MG_PC_LINE_X, is offered by the library only) */
+        fprintf(stderr, "mgpoisson: only -pc_type jacobi and -pc_type yline are built, and -pc_type altline (y- and x-line sweeps in turn)\n");
+        return 2;
+    }
     if ((v = get("-cycle")) && atoi(v) != 0) { fprintf(stderr, "mgpoisson: only -cycle 0 (V-cycle) is built\n"); return 2; }
     if ((v = get("-mesh"))) c.mesh = atoi(v);
     /* the V-cycle has one grid per level (src/poisson.c:61-71 guards the other combinations): -grids, when given, must agree */

@@ -299,14 +299,25 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
     if (cfg->dim != 2 && cfg->dim != 3) return mgfail(MGK_EINVAL, "mg_solver_create: dim must be 2 or 3");
     if (cfg->levels < 1 || cfg->levels > MG_MAX_LEVELS) return mgfail(MGK_EINVAL, "mg_solver_create: bad level count");
     if (cfg->npts < 3) return mgfail(MGK_EINVAL, "mg_solver_create: npts < 3");
-    if (cfg->pc_type != MG_PC_JACOBI && cfg->pc_type != MG_PC_LINE_Y) return mgfail(MGK_EINVAL, "mg_solver_create: pc_type must be jacobi (0) or yline (1)");
-    if (cfg->pc_type == MG_PC_LINE_Y) {
-        /* y-line Jacobi (mg_line.c): 2-D, fp64, one rank, Richardson */
-        if (cfg->dim != 2) return mgfail(MGK_EINVAL, "mg_solver_create: the y-line smoother is built for 2-D (not 3-D: that needs a plane smoother)");
-        if (cfg->precision != MG_PREC_FP64) return mgfail(MGK_EINVAL, "mg_solver_create: the y-line smoother is built for fp64 (not mixed precision)");
-        if (cfg->ksp_type != MG_KSP_RICHARDSON) return mgfail(MGK_EINVAL, "mg_solver_create: the y-line smoother is built for Richardson (not Chebyshev)");
-        if (cfg->nranks > 1) return mgfail(MGK_EINVAL, "mg_solver_create: the y-line smoother is built for one GPU (nranks == 1)");
-        if (!mg_line_tables || !mg_line_smooth) return mgfail(MGK_EINVAL, "mg_solver_create: this build has no y-line smoother (mg_line.c is not linked)");
+    if (cfg->pc_type < MG_PC_JACOBI || cfg->pc_type > MG_PC_LINE_ALT)
+        return mgfail(MGK_EINVAL, "mg_solver_create: pc_type must be jacobi (0), yline (1), xline (2) or altline (3)");
+    if (cfg->pc_type != MG_PC_JACOBI) {
+        /* the line smoothers (mg_line.c, mg_xline.c): 2-D, fp64, one rank, Richardson */
+        const char *name = cfg->pc_type == MG_PC_LINE_Y ? "y-line" : cfg->pc_type == MG_PC_LINE_X ? "x-line" : "alternating line";
+        const char *why = NULL;
+        char msg[192];
+        if (cfg->dim != 2) why = "2-D (not 3-D: that needs a plane smoother)";
+        else if (cfg->precision != MG_PREC_FP64) why = "fp64 (not mixed precision)";
+        else if (cfg->ksp_type != MG_KSP_RICHARDSON) why = "Richardson (not Chebyshev)";
+        else if (cfg->nranks > 1) why = "one GPU (nranks == 1)";
+        if (why) {
+            snprintf(msg, sizeof(msg), "mg_solver_create: the %s smoother is built for %s", name, why);
+            return mgfail(MGK_EINVAL, msg);
+        }
+        if (cfg->pc_type != MG_PC_LINE_X && (!mg_line_tables || !mg_line_smooth))
+            return mgfail(MGK_EINVAL, "mg_solver_create: this build has no y-line smoother (mg_line.c is not linked)");
+        if (cfg->pc_type != MG_PC_LINE_Y && (!mg_xline_tables || !mg_xline_smooth))
+            return mgfail(MGK_EINVAL, "mg_solver_create: this build has no x-line smoother (mg_xline.c is not linked)");
     }
     if (cfg->precision == MG_PREC_MIXED && (cfg->dim != 3 || cfg->ksp_type != MG_KSP_RICHARDSON))
         return mgfail(MGK_EINVAL, "mg_solver_create: mixed precision is built for 3-D, Richardson+Jacobi");
@@ -334,9 +345,9 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
     if (s->cfg.fuse < 0) s->cfg.fuse = MG_FUSE_DEFAULT;
     if (s->cfg.pair_min_n <= 0) s->cfg.pair_min_n = (cfg->dim == 3) ? 255 : 2047;   /* where a two-sweep pass beats two sweeps
                                                                                       * (255^3: 0.107 ms against 2 x 0.063) */
-    /* y-line Jacobi: the passes that bake point Jacobi in are off (bits 1, 3, 5, 8-15); the fused residual + norm (0) and residual +
+    /* line smoothers: the passes that bake point Jacobi in are off (bits 1, 3, 5, 8-15); the fused residual + norm (0) and residual +
      * restriction (2) stay, the coarse levels run by launch inside the HIP graph */
-    if (s->cfg.pc_type == MG_PC_LINE_Y) s->cfg.fuse &= ~MG_FUSE_POINT_JACOBI_PASSES;
+    if (s->cfg.pc_type != MG_PC_JACOBI) s->cfg.fuse &= ~MG_FUSE_POINT_JACOBI_PASSES;
     if (s->cfg.mesh) s->cfg.fuse &= ~MG_FUSE_NO_ROW_TABLE_FORM;   /* row-dependent coefficients (2-D, fp64): the same fused cycle on the row-table forms of the kernels */
     if (s->cfg.overlap < 0) s->cfg.overlap = 1;
     if (s->cfg.graph < 0) s->cfg.graph = 1;
@@ -394,7 +405,7 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         if (rc) { mg_solver_destroy(s); return mgfail(rc, "mg_solver_create: geometry"); }
         level_stencil(cfg->dim, L->n, L->coef, &L->h);
         L->dinv = 1.0 / L->coef[cfg->dim == 3 ? 3 : 2];      /* PCJACOBI: 1/diag(A) */
-        if (cfg->mesh || cfg->pc_type == MG_PC_LINE_Y) {
+        if (cfg->mesh || cfg->pc_type != MG_PC_JACOBI) {
             double *hc = (double *)malloc(sizeof(double) * 5 * (size_t)L->n), *hd = (double *)malloc(sizeof(double) * (size_t)L->n);
             if (cfg->mesh) level_row_tables(cfg->npts, cfg->mesh, l, L->n, hc, hd);
             else for (int i = 0; i < L->n; i++) {           /* uniform mesh: the level's five constants in every row */
@@ -403,7 +414,8 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
             }
             rc = upload(s, hc, 5 * (size_t)L->n, &L->ctab);
             if (!rc) rc = upload(s, hd, (size_t)L->n, &L->dtab);
-            if (!rc && cfg->pc_type == MG_PC_LINE_Y) rc = mg_line_tables(s, l, hc);
+            if (!rc && (cfg->pc_type == MG_PC_LINE_Y || cfg->pc_type == MG_PC_LINE_ALT)) rc = mg_line_tables(s, l, hc);
+            if (!rc && (cfg->pc_type == MG_PC_LINE_X || cfg->pc_type == MG_PC_LINE_ALT)) rc = mg_xline_tables(s, l, hc);
             free(hc); free(hd);
             if (rc) { mg_solver_destroy(s); return mgfail(rc, "mg_solver_create: coefficient tables"); }
         }
@@ -481,6 +493,7 @@ void mg_solver_destroy(mg_solver *s) {
             if (L->ltab) mgk_free(s->ctx, L->ltab);
             if (L->gtab) mgk_free(s->ctx, L->gtab);
             if (L->qtab) mgk_free(s->ctx, L->qtab);
+            if (L->xgtab) mgk_free(s->ctx, L->xgtab);
         }
         mgk_ctx_destroy(s->ctx);
     }
@@ -811,11 +824,11 @@ static int triple_ok(const mg_solver *s, int P, int l, int maxit) {
 
 /* pre: pre-smoothing, a restriction from this level follows (src/solver.c:1531 / :1536 before :1534 of the next level) */
 static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
-    if (s->cfg.pc_type == MG_PC_LINE_Y) {                           /* y-line Jacobi: every sweep in place (mg_line.c), no swap, no flag */
+    if (s->cfg.pc_type != MG_PC_JACOBI) {                           /* line smoothers: every sweep in place (mg_line.c, mg_xline.c), no swap, no flag */
         mg_fset *Fl = &s->L[l].f[0];
         Fl->pre_done = 0; Fl->jz_ready = 0; Fl->last_sweep_pending = 0;
         mgi_u_rewritten(Fl);
-        return mg_line_smooth(s, l, maxit);
+        return s->cfg.pc_type == MG_PC_LINE_Y ? mg_line_smooth(s, l, maxit) : mg_xline_smooth(s, l, maxit);   /* x sweeps, or y and x in turn */
     }
     if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV && !j3_2d_ok(s, P, l, maxit)) return smooth_chebyshev(s, l, maxit);
     mg_level *L = &s->L[l];
@@ -1378,7 +1391,7 @@ gathered:
 static int coarse_part(mg_solver *s, int P, int lg) {
     const int levels = s->levels, lend = s->ltail ? s->ltail : levels - 1;     /* last level the loops below handle themselves */
     for (int l = lg; l <= lend; l++) CHK(descend(s, P, l));
-    if (!s->ltail && (s->cfg.v[1] & 1) && s->cfg.pc_type != MG_PC_LINE_Y) {   /* restore the coarsest level's buffer identity (a line sweep swaps nothing) */
+    if (!s->ltail && (s->cfg.v[1] & 1) && s->cfg.pc_type == MG_PC_JACOBI) {   /* restore the coarsest level's buffer identity (a line sweep swaps nothing) */
         mg_fset *Cz = &s->L[levels - 1].f[P];
         CHK(mgk_d2d(s->ctx, Cz->tmp, Cz->u, (size_t)OPS[P].esz * (size_t)Cz->g.total, NULL));
         swap_ptr(&Cz->u, &Cz->tmp);

@@ -55,6 +55,8 @@ typedef struct mg_level {
     double *p2;             /* Chebyshev: third recurrence vector (fp64) */
     double *ltab, *gtab, *qtab;   /* y-line Jacobi (pc_type MG_PC_LINE_Y): device tables of the factorised y-tridiagonal part, n doubles each
                                    * (multipliers, 1 / pivot, N / pivot); ctab / dtab then exist on the uniform mesh too */
+    double *xgtab; long xgs;      /* x-line Jacobi (MG_PC_LINE_X / MG_PC_LINE_ALT): device table 1 / pivot of the factorised x-tridiagonal part,
+                                   * rows at a stride of xgs doubles (0: one row for every grid row -- the uniform mesh) */
 } mg_level;
 
 struct mg_solver {
@@ -112,6 +114,12 @@ extern int mg_cheby_tail(mg_solver *s) __attribute__((weak));      /* the levels
  * symbol, and mg_solver_create refuses the line smoother there */
 extern int mg_line_tables(mg_solver *s, int l, const double *ctab_host) __attribute__((weak));   /* factorise and upload level l's tables */
 extern int mg_line_smooth(mg_solver *s, int l, int maxit) __attribute__((weak));   /* KSPSolve on level l: maxit sweeps in place, no swap */
+/* x-line Jacobi and alternating line relaxation (MG_PC_LINE_X / MG_PC_LINE_ALT): mg_xline.c holds the only calls of mgk_xline_forward_f64 /
+ * mgk_xline_backward_f64 and makes the y sweeps of the alternation through mg_line_smooth; reached through WEAK references in the same way */
+extern int mg_xline_tables(mg_solver *s, int l, const double *ctab_host) __attribute__((weak));  /* factorise and upload level l's x table */
+extern int mg_xline_smooth(mg_solver *s, int l, int maxit) __attribute__((weak));  /* KSPSolve on level l: x sweeps, or y and x in turn */
+long mg_xline_stride(int n, int uniform);                                          /* row stride of the x table (mg_xline.c) */
+void mg_xline_factor(int n, int rows, const double *ctab, long gs, double *g);     /* the x table on the host (mg_xline.c) */
 
 /* the steps of mg_solver.c, for mg_fmg.c (fp64, one rank) */
 int    mgi_fail(int code, const char *what);            /* records the message for mg_last_error(), returns code */

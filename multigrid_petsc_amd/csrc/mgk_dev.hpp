@@ -38,6 +38,7 @@ int finish_to_host(mgk_ctx *c, int nparts, int nslots, hipStream_t s, double *ho
 int mgk_preload_kernels3();      // forces the code object of mgk_kernels3.hip to load (mgk_ctx_create)
 int mgk_preload_krylov();        // ... and that of mgk_krylov.hip
 int mgk_preload_line();          // ... and that of mgk_line.hip
+int mgk_preload_xline();         // ... and that of mgk_xline.hip
 #include "mgk_launch.hpp"        // the launch rules of the host side (they read the context and the knobs above)
 #define MGK_RESULT_SLOTS 64      // >= MGK_KRYLOV_MAX + 1: the dots of an Arnoldi step and the norm that follows them
 

@@ -72,6 +72,7 @@ extern "C" int mgk_ctx_create(mgk_ctx **out, int device) {
         int rc = mgk_preload_kernels3();
         if (!rc) rc = mgk_preload_krylov();
         if (!rc) rc = mgk_preload_line();
+        if (!rc) rc = mgk_preload_xline();
         if (rc) return rc;
     }
     *out = c;

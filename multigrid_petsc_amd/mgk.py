@@ -227,6 +227,9 @@ def _sigs(L):
         # y-line Jacobi: (ctab, ltab, gtab, b, u or None, z) / (qtab, scale, z, u or None, unew)
         "mgk_line_forward_f64": (i, [vp, G, vp, vp, vp, vp, vp, vp, vp]),
         "mgk_line_backward_f64": (i, [vp, G, vp, d, vp, vp, vp, vp]),
+        # x-line Jacobi: (ctab, gtab, gstride, b, u or None, z) / (ctab, gtab, gstride, scale, z, u or None, unew)
+        "mgk_xline_forward_f64": (i, [vp, G, vp, vp, C.c_long, vp, vp, vp, vp]),
+        "mgk_xline_backward_f64": (i, [vp, G, vp, vp, C.c_long, d, vp, vp, vp, vp]),
     }
     for name, (res, args) in S.items():
         f = getattr(L, name)

@@ -47,7 +47,7 @@ class Fuse(enum.IntFlag):
 
 
 _KSP = {"richardson": 0, "chebyshev": 1}
-_PC = {"jacobi": 0, "yline": 1}
+_PC = {"jacobi": 0, "yline": 1, "xline": 2, "altline": 3}
 
 
 def _lib():
@@ -162,7 +162,7 @@ class Solver:
         cfg.pair_min_n = pair_min_n
         cfg.slab_chunk = slab_chunk
         cfg.mesh = mesh
-        cfg.pc_type = _PC[pc_type]        # "yline": y-line Jacobi (2-D, fp64, one rank, Richardson; include/mgsolve.h)
+        cfg.pc_type = _PC[pc_type]        # "yline" / "xline": y- / x-line Jacobi, "altline": y and x sweeps in turn (2-D, fp64, one rank, Richardson; include/mgsolve.h)
         self.cfg = cfg
         self.h = C.c_void_p()
         self._chk(self.L.mg_solver_create(C.byref(self.h), C.byref(cfg), comm))

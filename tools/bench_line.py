@@ -1,14 +1,15 @@
-"""The y-line Jacobi cycle (pc_type="yline") against the point-Jacobi cycle and against V-cycle-preconditioned GMRES over it, one GPU, time
-to rtol 1e-7 at Richardson scale 0.8.  Per case ONE process holds two or three solvers of the same configuration; the samples alternate
+"""The line-smoothed cycles (pc_type="yline", and "altline": y- and x-line sweeps in turn) against the point-Jacobi cycle and against
+V-cycle-preconditioned GMRES over it, one GPU, time to rtol 1e-7 at Richardson scale 0.8.  Per case ONE process holds two or three solvers of the same configuration; the samples alternate
 between them (drift of the machine hits all alike), after one warm-up of each (first launches, the graph recording, the basis allocation).
 Reported per case: iterations, every sample of solve_seconds, and whether EVERY yline sample lies below EVERY sample of the others.
 
-    python tools/bench_line.py --case 4097:1:30 [--samples 5] [--only yline|jacobi|gmres] [--out FILE]      (run one case per process)
-    python tools/bench_line.py --kernels 4095,2047,1023 [--depths 8,16,32] [--reps 20] [--out FILE]
+    python tools/bench_line.py --case 4097:1:30 [--samples 5] [--only yline|altline|xline|jacobi|gmres] [--out FILE]      (run one case per process)
+    python tools/bench_line.py --kernels 4095,2047,1023 [--depths 8,16,32] [--xdepths 1,2,3] [--reps 20] [--out FILE]
 
 A case is npts:mesh[:restart]; with a restart length solve_gmres(restart) on a point-Jacobi solver is the third contender.  --only runs one
-alone (one solve of it under a kernel trace).  --kernels times the two passes of a sweep alone (from a guess, in place) on an n x n level with
-random row tables for every built prefetch depth: the measurement behind the default depth."""
+alone (one solve of it under a kernel trace).  --kernels times the two passes of a y sweep and of an x sweep alone (from a guess, in place) on
+an n x n level with random row tables for every built prefetch depth (y: rows, x: tiles of 16 columns): the measurement behind the default
+depths and the x : y pass ratio."""
 import argparse
 import ctypes as C
 import json
@@ -30,10 +31,11 @@ SCALE = 0.8
 
 def run(npts, mesh, restart, samples, only):
     levels = (npts - 1).bit_length() - 1
-    kinds = [only] if only else ["yline", "jacobi"] + (["gmres"] if restart else [])
-    S = {k: Solver(2, npts, levels, v=(3, 3), scale=SCALE, maxiter=2000, rtol=RTOL, mesh=mesh, pc_type="yline" if k == "yline" else "jacobi")
+    kinds = [only] if only else ["yline", "altline", "jacobi"] + (["gmres"] if restart else [])
+    S = {k: Solver(2, npts, levels, v=(3, 3), scale=SCALE, maxiter=2000, rtol=RTOL, mesh=mesh, pc_type="jacobi" if k == "gmres" else k)
          for k in kinds}
-    call = {"yline": lambda s: s.solve(), "jacobi": lambda s: s.solve(), "gmres": lambda s: s.solve_gmres(restart)}
+    call = {k: (lambda s: s.solve()) for k in ("yline", "altline", "xline", "jacobi")}
+    call["gmres"] = lambda s: s.solve_gmres(restart)
     secs, its = {k: [] for k in kinds}, {}
     for k, s in S.items():
         s.set_rhs_problem()
@@ -56,10 +58,12 @@ def run(npts, mesh, restart, samples, only):
     return row
 
 
-def kernels(sizes, depths, reps):
-    """microseconds of one forward and one backward pass (from a guess, in place) per size and prefetch depth, median of `reps`"""
+def kernels(sizes, depths, xdepths, reps):
+    """microseconds of one forward and one backward pass (from a guess, in place) per size and prefetch depth, median of `reps`: the y passes
+    under "depth_<rows>", the x passes under "xdepth_<tiles>" """
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import line_reference as LR
+    import xline_reference as XR
     from row_tables import _rt_tables
     from multigrid_petsc_amd.mgk import Mgk
     m = Mgk(0)
@@ -73,6 +77,10 @@ def kernels(sizes, depths, reps):
         b, u = m.to_field(geo, rng.uniform(-1, 1, n * n)), m.to_field(geo, rng.uniform(-1, 1, n * n))
         z = m.field(geo)
         t = [m.upload(x) for x in (ct, l, g, q)]
+        gs = (n + 15) // 16 * 16
+        xg = np.zeros((n, gs))
+        xg[:, :n] = XR.table(ct)
+        t.append(m.upload(xg))
         G = C.byref(geo)
         row = {"n": n, "reps": reps}
         for d in depths:
@@ -91,6 +99,22 @@ def kernels(sizes, depths, reps):
                     us["forward"].append(1e6 * (t1 - t0))
                     us["backward"].append(1e6 * (t2 - t1))
             row["depth_%d" % d] = {k: {"median_us": statistics.median(v), "min_us": min(v)} for k, v in us.items()}
+        for d in xdepths:
+            L.mgk_set_tuning(-1, d)
+            us = {"forward": [], "backward": []}
+            for r in range(reps + 2):
+                m.sync()
+                t0 = time.perf_counter()
+                m._chk(L.mgk_xline_forward_f64(m.ctx, G, t[0], t[4], gs, b, u, z, None))
+                m.sync()
+                t1 = time.perf_counter()
+                m._chk(L.mgk_xline_backward_f64(m.ctx, G, t[0], t[4], gs, 1e-3, z, u, u, None))
+                m.sync()
+                t2 = time.perf_counter()
+                if r >= 2:
+                    us["forward"].append(1e6 * (t1 - t0))
+                    us["backward"].append(1e6 * (t2 - t1))
+            row["xdepth_%d" % d] = {k: {"median_us": statistics.median(v), "min_us": min(v)} for k, v in us.items()}
         L.mgk_set_tuning(-1, -1)
         for p in [b, u, z] + t:
             m.free(p)
@@ -103,14 +127,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default=None, help="npts:mesh[:restart]")
     ap.add_argument("--samples", type=int, default=5)
-    ap.add_argument("--only", default=None, choices=["yline", "jacobi", "gmres"])
+    ap.add_argument("--only", default=None, choices=["yline", "altline", "xline", "jacobi", "gmres"])
     ap.add_argument("--kernels", default=None, help="level sizes n (n + 1 a power of two), comma separated")
     ap.add_argument("--depths", default="8,16,32")
+    ap.add_argument("--xdepths", default="1,2,3")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.kernels:
-        rows = kernels([int(x) for x in a.kernels.split(",")], [int(x) for x in a.depths.split(",")], a.reps)
+        rows = kernels([int(x) for x in a.kernels.split(",")], [int(x) for x in a.depths.split(",") if x], [int(x) for x in a.xdepths.split(",") if x], a.reps)
     elif a.case:
         f = a.case.split(":")
         rows = [run(int(f[0]), int(f[1]), int(f[2]) if len(f) > 2 else 0, a.samples, a.only)]
