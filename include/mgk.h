@@ -609,6 +609,38 @@ int  mgk_line_chunk_reduce_f64(mgk_ctx *ctx, const mgk_geom *g, int c, const dou
 int  mgk_line_chunk_correct_f64(mgk_ctx *ctx, const mgk_geom *g, int c, const double *vtab, const double *wtab, double scale,
                                 const double *t, const double *u, double *unew, void *stream);
 
+/* ---- the x-line sweep in chunks (csrc/mg_xline_chunk.c; kernels in csrc/mgk_xline_chunk.hip) ----
+ * The sweep of mgk_xline_forward_f64 / mgk_xline_backward_f64 with the tridiagonal systems of the rows partitioned: period c, a positive multiple
+ * of 16, K = nx / c, column s_q = q c + c - 1 is separator q, the columns [k c, min(k c + c - 1, nx)) are chunk k (0 <= k <= K), solved
+ * independently of each other; the separators of a row are solved by their Schur complement and the chunks corrected by two spike vectors.
+ * Device tables (mg_xline_chunk.c): gtab, vtab, wtab laid out as mgk_xline_forward_f64's gtab ([i gstride + j]; gstride == 0: one row for every
+ * grid row) -- g restarted in every chunk, the spikes, all three 0 in the separator columns; vtab and wtab 16-byte aligned and gstride even.
+ * SLtab, SGtab, SQtab: the factorised Schur rows, entry [q sstride + i] for separator q of grid row i (sstride == 0: one value per separator
+ * for every row, entry [q]; otherwise sstride >= ny).  Four passes over one scratch field t and a separator workspace sep of four planes R, XL, XR, XI of
+ * K rows of ss doubles, ss = ny rounded up to 16: element (plane p, separator q, row i) at sep[(p K + q) ss + i].  fp64, every product and sum
+ * rounded on its own; l_{i,j} = W_i g_{i,j-1} and q_{i,j} = E_i g_{i,j} are formed by the kernels as in the plain passes:
+ *   mgk_xline_chunk_forward_f64    r as mgk_xline_forward_f64 (u == NULL: r = b); in every chunk y_a = r_a, y_j = r_j - l_j y_{j-1}, t_j = y_j g_j;
+ *                                  t_s = r_s in the separator columns and R[q][i] = r_{i,s_q}.  t must not alias b, u or sep.   32 (24) B per unknown
+ *   mgk_xline_chunk_backward_f64   in every chunk x'_{b-1} = t_{b-1}, x'_j = t_j - q_j x'_{j+1}, in place in t (the separator columns stay);
+ *                                  XL[k][i] = x'_{i,s_k - 1} (k < K), XR[k-1][i] = x'_{i,k c} (k > 0, a chunk that is not empty)         24 B
+ *   mgk_xline_chunk_reduce_f64     rho_q = (R_q - W_i XL_q) - E_i XR_q (the last term only if s_q < nx - 1); Y_0 = rho_0,
+ *                                  Y_q = rho_q - SL_q Y_{q-1}, Z_q = Y_q SG_q; xi_{K-1} = Z_{K-1}, xi_q = Z_q - SQ_q xi_{q+1}; XI[q][i] = xi_q.  4 K rows
+ *   mgk_xline_chunk_correct_f64    chunk k: x_j = (t_j - xi_{k-1} v_j) - xi_k w_j (no first term for k = 0, no second for k = K); x_s = xi_q;
+ *                                  unew = u + scale x (u == NULL: scale x).  unew may be u, not t; t and sep stay.           40 (32) B per unknown
+ * (with gstride == 0 the tables stay in cache: 8 B less in the first two passes, 16 B less in the last.)  With c > nx (K = 0) the four passes are
+ * the two passes of the plain sweep, bit for bit, and sep is not touched (it may be NULL).  Nothing outside the interior of an output is
+ * written, neither the ghost ring nor the padding of an input is read, and an entry of sep that the definition never forms (XR[K-1] when
+ * s_{K-1} = nx - 1) is neither written nor read.  2-D, c a positive multiple of 16, at most 65534 separators, the pitch, gstride and sstride at most 2^21 doubles
+ * (MGK_EINVAL otherwise).  Stores: by size, mgk_set_tuning(variant = 0 / 1) forces one policy, as the y-line passes. */
+int  mgk_xline_chunk_forward_f64(mgk_ctx *ctx, const mgk_geom *g, int c, const double *atab, const double *gtab, long gstride,
+                                 const double *b, const double *u, double *t, double *sep, void *stream);
+int  mgk_xline_chunk_backward_f64(mgk_ctx *ctx, const mgk_geom *g, int c, const double *atab, const double *gtab, long gstride,
+                                  double *t, double *sep, void *stream);
+int  mgk_xline_chunk_reduce_f64(mgk_ctx *ctx, const mgk_geom *g, int c, const double *atab, const double *SLtab, const double *SGtab,
+                                const double *SQtab, long sstride, double *sep, void *stream);
+int  mgk_xline_chunk_correct_f64(mgk_ctx *ctx, const mgk_geom *g, int c, const double *vtab, const double *wtab, long gstride, double scale,
+                                 const double *t, const double *sep, const double *u, double *unew, void *stream);
+
 /* Named values of mgk_set_tuning's first argument.  From 30 up a value selects ONE form of ONE launcher (every other launcher takes it as
  * "no special form"); the values below 30 are read three ways, see the table under the enum.  MGK_TUNE_STORE_* name the 0 / 1 reading of
  * the Krylov and line passes.  mgk_set_tuning takes any int: a value nothing reads selects nothing. */

@@ -120,6 +120,15 @@ typedef struct mg_config {
                          * y-line sweep for even k and an x-line sweep for odd k -- the same number of sweeps as MG_PC_LINE_Y, and a cycle count
                          * independent of npts on meshes 0, 1 and 2.  Both under the conditions of MG_PC_LINE_Y, with
                          * the same refusals */
+    int xline_chunk;    /* (0, default: off) c > 0, a multiple of 16: every x-line sweep (MG_PC_LINE_X, the odd sweeps of MG_PC_LINE_ALT) solves its
+                         * tridiagonal systems in chunks of c columns -- column q c + c - 1 is a separator, the c - 1 columns before it a
+                         * chunk; the chunks are solved independently, the n / c separators of a row by their Schur complement, the chunks
+                         * corrected by two spike vectors (line_chunk turned by 90 degrees; two more tables of the size
+                         * of the x table, three of n / c values per row and a workspace of 4 n / c rows per level) -- so that a pass runs on
+                         * n / c + 1 times as many waves: four passes per sweep (mgk_xline_chunk_*_f64) instead of two.  The arithmetic
+                         * differs from the plain sweep by rounding (its own definition, tests/xchunkline_reference.py); a level with
+                         * n < c keeps the plain sweep.  Independent of line_chunk.  < 0, not a multiple of 16, or > 0 with
+                         * MG_PC_JACOBI / MG_PC_LINE_Y: MGK_EINVAL */
     int line_chunk;     /* (0, default: off) c >= 2: every y-line sweep (MG_PC_LINE_Y, the even sweeps of MG_PC_LINE_ALT) solves its tridiagonal
                          * systems in chunks of c rows -- row j c + c - 1 is a separator, the c - 1 rows before it a chunk; the chunks are
                          * solved independently, the n / c separators by their Schur complement, the chunks corrected by two spike

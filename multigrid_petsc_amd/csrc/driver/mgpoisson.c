@@ -90,6 +90,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "mgpoisson: only -pc_type jacobi and -pc_type yline are built, and -pc_type altline (y- and x-line sweeps in turn)\n");
         return 2;
     }
+    if ((v = get("-xline_chunk"))) c.xline_chunk = atoi(v);                         /* the x-line sweeps in chunks of that many columns (0: whole) */
     if ((v = get("-line_chunk"))) c.line_chunk = atoi(v);                           /* the y-line sweeps in chunks of that many rows (0: whole) */
     if ((v = get("-cycle")) && atoi(v) != 0) { fprintf(stderr, "mgpoisson: only -cycle 0 (V-cycle) is built\n"); return 2; }
     if ((v = get("-mesh"))) c.mesh = atoi(v);

@@ -251,6 +251,7 @@ void mg_config_default(mg_config *c) {
     c->graph = -1;
     c->pair_min_n = 0;
     c->slab_chunk = -1;
+    c->xline_chunk = 0;                          /* the x-line sweeps whole (mg_xline.c) */
     c->line_chunk = 0;                           /* the y-line sweeps whole (mg_line.c) */
 }
 
@@ -326,6 +327,12 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         return mgfail(MGK_EINVAL, "mg_solver_create: line_chunk splits y-line sweeps: it needs pc_type yline or altline (not jacobi or xline)");
     if (cfg->line_chunk > 0 && (!mg_line_chunk_tables || !mg_line_chunk_smooth))
         return mgfail(MGK_EINVAL, "mg_solver_create: this build has no chunked y-line sweep (mg_line_chunk.c is not linked)");
+    if (cfg->xline_chunk < 0 || cfg->xline_chunk % 16 != 0)
+        return mgfail(MGK_EINVAL, "mg_solver_create: xline_chunk must be 0 (off) or a positive multiple of 16 columns");
+    if (cfg->xline_chunk > 0 && (cfg->pc_type == MG_PC_JACOBI || cfg->pc_type == MG_PC_LINE_Y))
+        return mgfail(MGK_EINVAL, "mg_solver_create: xline_chunk splits x-line sweeps: it needs pc_type xline or altline (not jacobi or yline)");
+    if (cfg->xline_chunk > 0 && (!mg_xline_chunk_tables || !mg_xline_chunk_smooth))
+        return mgfail(MGK_EINVAL, "mg_solver_create: this build has no chunked x-line sweep (mg_xline_chunk.c is not linked)");
     if (cfg->precision == MG_PREC_MIXED && (cfg->dim != 3 || cfg->ksp_type != MG_KSP_RICHARDSON))
         return mgfail(MGK_EINVAL, "mg_solver_create: mixed precision is built for 3-D, Richardson+Jacobi");
     /* npts-1 must be divisible by 2^(levels-1) and the coarsest grid must keep >= 1 unknown */
@@ -424,6 +431,7 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
             if (!rc && (cfg->pc_type == MG_PC_LINE_Y || cfg->pc_type == MG_PC_LINE_ALT)) rc = mg_line_tables(s, l, hc);
             if (!rc && cfg->line_chunk > 0) rc = mg_line_chunk_tables(s, l, hc);     /* (pc_type yline / altline: checked above) */
             if (!rc && (cfg->pc_type == MG_PC_LINE_X || cfg->pc_type == MG_PC_LINE_ALT)) rc = mg_xline_tables(s, l, hc);
+            if (!rc && cfg->xline_chunk > 0) rc = mg_xline_chunk_tables(s, l, hc);   /* (pc_type xline / altline: checked above) */
             free(hc); free(hd);
             if (rc) { mg_solver_destroy(s); return mgfail(rc, "mg_solver_create: coefficient tables"); }
         }
@@ -503,6 +511,8 @@ void mg_solver_destroy(mg_solver *s) {
             if (L->qtab) mgk_free(s->ctx, L->qtab);
             if (L->xgtab) mgk_free(s->ctx, L->xgtab);
             if (L->chunktab) mgk_free(s->ctx, L->chunktab);
+            if (L->xchunktab) mgk_free(s->ctx, L->xchunktab);
+            if (L->xchunksep) mgk_free(s->ctx, L->xchunksep);
         }
         mgk_ctx_destroy(s->ctx);
     }

@@ -59,6 +59,8 @@ typedef struct mg_level {
                                    * rows at a stride of xgs doubles (0: one row for every grid row -- the uniform mesh) */
     double *chunktab;             /* y-line sweeps in chunks (mg_config.line_chunk = c, mg_line_chunk.c): one device array [l g q v w | L G Q], five
                                    * tables of n doubles and three of n / c; NULL on a level with n < c, which keeps the plain sweep */
+    double *xchunktab, *xchunksep; /* x-line sweeps in chunks (mg_config.xline_chunk = c, mg_xline_chunk.c): one device array [g | v | w | SL SG SQ]
+                                   * and the separator workspace of 4 (n / c) rows; NULL on a level with n < c, which keeps the plain sweep */
 } mg_level;
 
 struct mg_solver {
@@ -125,6 +127,11 @@ extern int mg_xline_smooth(mg_solver *s, int l, int maxit) __attribute__((weak))
  * in a build without it */
 extern int mg_line_chunk_tables(mg_solver *s, int l, const double *ctab_host) __attribute__((weak));   /* level l's tables; none when n < c */
 extern int mg_line_chunk_smooth(mg_solver *s, int l, int maxit) __attribute__((weak));   /* mg_line_smooth on a level with chunk tables */
+/* the x sweeps in chunks (mg_config.xline_chunk > 0): mg_xline_chunk.c holds the only calls of the four mgk_xline_chunk_*_f64 kernels; mg_solver.c
+ * (the tables) and mg_xline.c (the x sweeps of a level that has them) reach it through WEAK references, and mg_solver_create refuses
+ * xline_chunk > 0 in a build without it */
+extern int mg_xline_chunk_tables(mg_solver *s, int l, const double *ctab_host) __attribute__((weak));  /* level l's tables; none when n < c */
+extern int mg_xline_chunk_smooth(mg_solver *s, int l, int maxit) __attribute__((weak));  /* maxit x sweeps on a level with chunk tables */
 long mg_xline_stride(int n, int uniform);                                          /* row stride of the x table (mg_xline.c) */
 void mg_xline_factor(int n, int rows, const double *ctab, long gs, double *g);     /* the x table on the host (mg_xline.c) */
 

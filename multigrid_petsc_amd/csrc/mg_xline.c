@@ -15,7 +15,7 @@
  * A sweep is a forward pass (residual, forward substitution, z = y g -> the level's tmp) and a backward pass (back substitution and the
  * update, in place in u): no buffer is swapped.  MG_PC_LINE_ALT: within one KSPSolve sweep k is a y-line sweep (mg_line.c) for even k and
  * an x-line sweep for odd k.  This file is the only host code that calls the two kernels; mg_solver.c refers to it weakly
- * (mg_solver_internal.h).
+ * (mg_solver_internal.h).  With mg_config.xline_chunk the x sweeps of a level that has separators are mg_xline_chunk.c's.
  */
 #include "mg_solver_internal.h"
 #include <stdlib.h>
@@ -68,6 +68,13 @@ int mg_xline_smooth(mg_solver *s, int l, int maxit) {
         if (alt && !(it & 1)) {                                 /* a y sweep from the state this sweep finds: mg_line.c's, one sweep */
             F->guess_nonzero = !zero;
             const int rc = mg_line_smooth(s, l, 1);
+            F->guess_nonzero = guess;
+            if (rc) return rc;
+            continue;
+        }
+        if (L->xchunktab) {                                     /* mg_config.xline_chunk, a level with separators: mg_xline_chunk.c's four passes */
+            F->guess_nonzero = !zero;
+            const int rc = mg_xline_chunk_smooth(s, l, 1);
             F->guess_nonzero = guess;
             if (rc) return rc;
             continue;

@@ -74,6 +74,7 @@ extern "C" int mgk_ctx_create(mgk_ctx **out, int device) {
         if (!rc) rc = mgk_preload_line();
         if (!rc) rc = mgk_preload_xline();
         if (!rc) rc = mgk_preload_line_chunk();
+        if (!rc) rc = mgk_preload_xline_chunk();
         if (rc) return rc;
     }
     *out = c;

@@ -236,6 +236,12 @@ def _sigs(L):
         "mgk_line_chunk_backward_f64": (i, [vp, G, i, vp, vp, vp]),
         "mgk_line_chunk_reduce_f64": (i, [vp, G, i, vp, vp, vp, vp, vp, vp]),
         "mgk_line_chunk_correct_f64": (i, [vp, G, i, vp, vp, d, vp, vp, vp, vp]),
+        # the x-line sweep in chunks of c columns: (c, ctab, gtab, gstride, b, u or None, t, sep) / (c, ctab, gtab, gstride, t, sep) /
+        # (c, ctab, SLtab, SGtab, SQtab, sstride, sep) / (c, vtab, wtab, gstride, scale, t, sep, u or None, unew)
+        "mgk_xline_chunk_forward_f64": (i, [vp, G, i, vp, vp, C.c_long, vp, vp, vp, vp, vp]),
+        "mgk_xline_chunk_backward_f64": (i, [vp, G, i, vp, vp, C.c_long, vp, vp, vp]),
+        "mgk_xline_chunk_reduce_f64": (i, [vp, G, i, vp, vp, vp, vp, C.c_long, vp, vp]),
+        "mgk_xline_chunk_correct_f64": (i, [vp, G, i, vp, vp, C.c_long, d, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in S.items():
         f = getattr(L, name)
