@@ -681,7 +681,9 @@ enum mgk_tune {
     MGK_TUNE_J3_2D_STORE_NT    = 61,   /* jacobi3_2d: non-temporal stores whatever the field size */
     MGK_TUNE_J3_3D_TY2         = 62,   /* jacobi3_3d: wave tiles of 2 rows */
     MGK_TUNE_J3_3D_TY3         = 63,   /* jacobi3_3d: wave tiles of 3 rows (what the norm form always takes) */
-    MGK_TUNE_J3_3D_ROWWISE     = 64    /* jacobi3_3d: the sweeps row by row instead of term by term over the rows */
+    MGK_TUNE_J3_3D_ROWWISE     = 64,   /* jacobi3_3d: the sweeps row by row instead of term by term over the rows */
+    MGK_TUNE_NO_EXACT_FMA      = 65    /* the fp64 3-D constant-coefficient kernels: the generic stencil sum (multiply, then add) even where all six
+                                          off-diagonal coefficients are +-2^e, e >= 0, and the exact-FMA form would be taken (same results) */
 };
 
 /* tuning knobs (profiling only), per calling thread: <=0 keeps the built-in choice.  They are GLOBAL to that thread, not per kernel -- set

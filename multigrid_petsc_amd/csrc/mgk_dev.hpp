@@ -155,6 +155,15 @@ __device__ __forceinline__ void stv_stream(float *p, const V16<float> &v) {
 #endif
 }
 
+// one further term of the canonical stencil sum: t + a * x.  EX (fp64 only): the launcher has checked that a is +-2^e with e >= 0 (exact_fma7,
+// mgk_launch.hpp), so a * x is exact and the fused multiply-add rounds the same real number t + a x to the same double -- one instruction
+// instead of two (the only difference: |a x| beyond the double range).  An explicit fma is not touched by -ffp-contract=off
+template <bool EX> __device__ __forceinline__ double madd(double t, double a, double x) {
+    if constexpr (EX) return __builtin_fma(a, x, t);
+    else return t + a * x;
+}
+template <bool EX> __device__ __forceinline__ float madd(float t, float a, float x) { return t + a * x; }      // fp32 keeps the generic form
+
 // lane i <- lane i-1 / lane i+1 of the wavefront.  DPP form: whole-wavefront shifts (wave_shr:1 / wave_shl:1) on the vector ALU
 // instead of ds_bpermute on the LDS pipe; lane 0 / 63 keep their own value (the callers replace it by the wave-edge value).
 template <bool DPP> __device__ __forceinline__ double lane_up(double v) {

@@ -1470,7 +1470,8 @@ __global__ void __launch_bounds__(64 * WX) k_jacobi2b(const J2Args<T> a) {
 // pre-smoothing sweeps of cycle k+1 (:1531).
 // NORM == 2: the sum of squares of the residual the SECOND sweep forms, i.e. of b - A J(u): the norm that closes a cycle whose last
 // post-smoothing sweep is this pass's first sweep (the iterate J(u) itself is never stored: the caller keeps u and owes one sweep).
-template <typename T, int WX, int FORM, int NORM = 0>
+// EX: the six off-diagonal terms of both sweeps are exact fused multiply-adds (madd, mgk_dev.hpp; chosen by the launcher, exact_fma7)
+template <typename T, int WX, int FORM, int NORM = 0, bool EX = false>
 __global__ void __launch_bounds__(64 * WX) k_jacobi2r(const J2Args<T> a) {
     // FORM bit 0: unconditional loads with rows / planes clamped on the scalar unit (full-row shapes only: no lane outside the
     // grid; whatever a clamped load brings in only reaches first-sweep values that are forced to 0 anyway); bit 1: DPP lane shifts
@@ -1581,12 +1582,12 @@ __global__ void __launch_bounds__(64 * WX) k_jacobi2r(const J2Args<T> a) {
                     const T wv = (e == 0) ? Wv : ub[rr].v[e - 1 < 0 ? 0 : e - 1];
                     const T ev = (e == VX - 1) ? Ev : ub[rr].v[e + 1 > VX - 1 ? VX - 1 : e + 1];
                     T s = a.a0 * ua[rr].v[e];
-                    s = s + a.a1 * ub[rr - 1].v[e];
-                    s = s + a.a2 * wv;
+                    s = madd<EX>(s, a.a1, ub[rr - 1].v[e]);
+                    s = madd<EX>(s, a.a2, wv);
                     s = s + a.a3 * ub[rr].v[e];
-                    s = s + a.a4 * ev;
-                    s = s + a.a5 * ub[rr + 1].v[e];
-                    s = s + a.a6 * uc[rr].v[e];
+                    s = madd<EX>(s, a.a4, ev);
+                    s = madd<EX>(s, a.a5, ub[rr + 1].v[e]);
+                    s = madd<EX>(s, a.a6, uc[rr].v[e]);
                     const T res = b1[q].v[e] - s;
                     const T zz = res * a.dinv;
                     o.v[e] = ub[rr].v[e] + a.scale * zz;
@@ -1627,12 +1628,12 @@ __global__ void __launch_bounds__(64 * WX) k_jacobi2r(const J2Args<T> a) {
                     const T wv = (e == 0) ? Wv : wc[j].v[e - 1 < 0 ? 0 : e - 1];
                     const T ev = (e == VX - 1) ? Ev : wc[j].v[e + 1 > VX - 1 ? VX - 1 : e + 1];
                     T s = a.a0 * wm[j].v[e];
-                    s = s + a.a1 * sv.v[e];
-                    s = s + a.a2 * wv;
+                    s = madd<EX>(s, a.a1, sv.v[e]);
+                    s = madd<EX>(s, a.a2, wv);
                     s = s + a.a3 * wc[j].v[e];
-                    s = s + a.a4 * ev;
-                    s = s + a.a5 * nv.v[e];
-                    s = s + a.a6 * wp[j].v[e];
+                    s = madd<EX>(s, a.a4, ev);
+                    s = madd<EX>(s, a.a5, nv.v[e]);
+                    s = madd<EX>(s, a.a6, wp[j].v[e]);
                     const T res = b0[j].v[e] - s;
                     const T zz = res * a.dinv;
                     o.v[e] = wc[j].v[e] + a.scale * zz;
@@ -1888,7 +1889,7 @@ __global__ void __launch_bounds__(64 * WX) k_pj2r(const PJ2Args a) {
 }
 // ZU (FMG interpolation, mgk_interp_jacobi2_f64): the old u is not read -- every plane of it counts as zero, so the pass makes
 // J(J(0 + P uc)) from b and uc alone (17 instead of 25 B per unknown); the correction adds to 0.0 exactly as mgk_prolong_add_f64 on a zeroed field
-template <int WX, bool SLAB, bool ZU = false>
+template <int WX, bool SLAB, bool ZU = false, bool EX = false>
 __global__ void __launch_bounds__(64 * WX) k_pj2r3(const PJ2Args a) {
     typedef double T;
     constexpr int VX = 2, TY = 4, R1 = TY + 4, R2 = TY + 2, TX = 64 * VX * WX, LW = TX + 2 * VX, NCR = 5, LC = 64 * WX + 4;
@@ -2036,12 +2037,12 @@ __global__ void __launch_bounds__(64 * WX) k_pj2r3(const PJ2Args a) {
                         const T wv = (e == 0) ? Wv : ub[rr].v[0];
                         const T ev = (e == VX - 1) ? Ev : ub[rr].v[VX - 1];
                         T s = a.a0 * ua[rr].v[e];
-                        s = s + a.a1 * ub[rr - 1].v[e];
-                        s = s + a.a2 * wv;
+                        s = madd<EX>(s, a.a1, ub[rr - 1].v[e]);
+                        s = madd<EX>(s, a.a2, wv);
                         s = s + a.a3 * ub[rr].v[e];
-                        s = s + a.a4 * ev;
-                        s = s + a.a5 * ub[rr + 1].v[e];
-                        s = s + a.a6 * uc[rr].v[e];
+                        s = madd<EX>(s, a.a4, ev);
+                        s = madd<EX>(s, a.a5, ub[rr + 1].v[e]);
+                        s = madd<EX>(s, a.a6, uc[rr].v[e]);
                         const T res = b1[q].v[e] - s;
                         const T zz = res * a.dinv;
                         o.v[e] = ub[rr].v[e] + a.scale * zz;
@@ -2081,12 +2082,12 @@ __global__ void __launch_bounds__(64 * WX) k_pj2r3(const PJ2Args a) {
                         const T wv = (e == 0) ? Wv : wc[j].v[0];
                         const T ev = (e == VX - 1) ? Ev : wc[j].v[VX - 1];
                         T s = a.a0 * wm[j].v[e];
-                        s = s + a.a1 * sv.v[e];
-                        s = s + a.a2 * wv;
+                        s = madd<EX>(s, a.a1, sv.v[e]);
+                        s = madd<EX>(s, a.a2, wv);
                         s = s + a.a3 * wc[j].v[e];
-                        s = s + a.a4 * ev;
-                        s = s + a.a5 * nv.v[e];
-                        s = s + a.a6 * wp[j].v[e];
+                        s = madd<EX>(s, a.a4, ev);
+                        s = madd<EX>(s, a.a5, nv.v[e]);
+                        s = madd<EX>(s, a.a6, wp[j].v[e]);
                         const T res = b0[j].v[e] - s;
                         const T zz = res * a.dinv;
                         o.v[e] = wc[j].v[e] + a.scale * zz;
@@ -2140,8 +2141,9 @@ static int prolong_jacobi2(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, c
     const int w = (gf->nx + 1) / 128;
     // the marching loop unrolled by three, the plane roles permuted instead of copied: 1023^3 4.80 against 4.90 ms, 511^3 0.651 -> 0.601 ms
     // (253 VGPRs, two blocks per CU); MGK_TUNE_PJ2_COPY: the copying form k_pj2r (not built from the zero guess)
-    if (ZU) LAUNCH_WX(width_48, w, (k_pj2r3<WX, false, true>), nblk, S(c, stream), a);
-    else if (g_variant != MGK_TUNE_PJ2_COPY) LAUNCH_WX(width_48, w, (k_pj2r3<WX, false>), nblk, S(c, stream), a);
+    const bool ex = exact_fma7(coef);                          // all six off-diagonals +-2^e: the exact-FMA form of the stencil sums (same results)
+    if (ZU) LAUNCH_WX_EX(width_48, w, double, ex, (k_pj2r3<WX, false, true, EX>), nblk, S(c, stream), a);
+    else if (g_variant != MGK_TUNE_PJ2_COPY) LAUNCH_WX_EX(width_48, w, double, ex, (k_pj2r3<WX, false, false, EX>), nblk, S(c, stream), a);
     else LAUNCH_WX(width_48, w, (k_pj2r<WX>), nblk, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
@@ -2231,8 +2233,9 @@ static int jacobi2(mgk_ctx *c, const mgk_geom *g, const double *coef, double din
             return fail(MGK_EINVAL, "mgk_jacobi2_sumsq: built for fp64 full-row shapes (n = 127, 255, 511, 1023)");
         a.partials = c->partials + part_off;
         if constexpr (sizeof(T) == 8) {                                 // (the norm forms are built for fp64 only)
-            if (norm_mode == 2) LAUNCH_WX(width_1248, w, (k_jacobi2r<T, WX, 3, 2>), nblk, s, a);
-            else LAUNCH_WX(width_1248, w, (k_jacobi2r<T, WX, 3, 1>), nblk, s, a);
+            const bool exn = exact_fma7(coef);
+            if (norm_mode == 2) LAUNCH_WX_EX(width_1248, w, T, exn, (k_jacobi2r<T, WX, 3, 2, EX>), nblk, s, a);
+            else LAUNCH_WX_EX(width_1248, w, T, exn, (k_jacobi2r<T, WX, 3, 1, EX>), nblk, s, a);
         }
         HIPCHK(hipGetLastError());
         *norm_parts = (int)nblk;
@@ -2264,7 +2267,7 @@ static int jacobi2(mgk_ctx *c, const mgk_geom *g, const double *coef, double din
         }
     } else {
         if (full) {
-            LAUNCH_WX(width_1248, w, (k_jacobi2r<T, WX, 3>), nblk, s, a);
+            LAUNCH_WX_EX(width_1248, w, T, exact_fma7(coef), (k_jacobi2r<T, WX, 3, 0, EX>), nblk, s, a);
         } else {
             LAUNCH_WX(width_1248, w, (k_jacobi2r<T, WX, 0>), nblk, s, a);
         }
@@ -3990,7 +3993,7 @@ __global__ void __launch_bounds__(64 * WX) k_resrestrict(const RRArgs<T> a) {
 // (rows beyond the ghost row alias the ghost row, planes beyond the chunk alias its last plane), and the shapes are restricted to
 // full rows (nx + 1 a multiple of the wave row) so that no lane lies outside the grid.  No exec masking, no branch per load.
 
-template <typename T, int WX, int PD, int FORM>
+template <typename T, int WX, int PD, int FORM, bool EX = false>
 __global__ void __launch_bounds__(64 * WX) k_rrrow(const RRArgs<T> a) {
     constexpr bool DPP = (FORM & 2) != 0;
     constexpr int VX = 16 / sizeof(T), NCJ = VX / 2;
@@ -4098,11 +4101,11 @@ __global__ void __launch_bounds__(64 * WX) k_rrrow(const RRArgs<T> a) {
                         const T wv = (e == 0) ? Wv : c.v[e > 0 ? e - 1 : 0];
                         const T ev = (e == VX - 1) ? Ev : c.v[e < VX - 1 ? e + 1 : e];
                         T t = a.a0 * U[cm][r + 1].v[e];
-                        t = t + a.a1 * U[cc][r].v[e];
-                        t = t + a.a2 * wv;
+                        t = madd<EX>(t, a.a1, U[cc][r].v[e]);
+                        t = madd<EX>(t, a.a2, wv);
                         t = t + a.a3 * c.v[e];
-                        t = t + a.a4 * ev;
-                        t = t + a.a5 * U[cc][r + 2].v[e];
+                        t = madd<EX>(t, a.a4, ev);
+                        t = madd<EX>(t, a.a5, U[cc][r + 2].v[e]);
                         res[r].v[e] = t;
                     }
                     }
@@ -4117,7 +4120,7 @@ __global__ void __launch_bounds__(64 * WX) k_rrrow(const RRArgs<T> a) {
                     } else {
 #pragma unroll
                     for (int e = 0; e < VX; e++) {
-                        const T t = res[r].v[e] + a.a6 * U[cp][r + 1].v[e];
+                        const T t = madd<EX>(res[r].v[e], a.a6, U[cp][r + 1].v[e]);
                         res[r].v[e] = rok[r] ? B[cc][r].v[e] - t : (T)0;
                     }
                     }
@@ -4605,8 +4608,8 @@ template <typename T> static bool jrow_ok(const mgk_geom *g) {
     return g_variant == MGK_TUNE_ROW_DPP || (g_variant < 0 && sizeof(T) == 8 && g->nx + 1 >= 1024);
 }
 template <typename T, int PD, int FORM>
-static void launch_rrrow(int w, unsigned nblk, hipStream_t s, const RRArgs<T> &a) {
-    LAUNCH_WX(width_1248, w, (k_rrrow<T, WX, PD, FORM>), nblk, s, a);
+static void launch_rrrow(int w, unsigned nblk, hipStream_t s, const RRArgs<T> &a, bool ex) {
+    LAUNCH_WX_EX(width_1248, w, T, ex, (k_rrrow<T, WX, PD, FORM, EX>), nblk, s, a);
 }
 template <typename T, int PD, int FORM>
 static void launch_pjrow(int w, unsigned nblk, hipStream_t s, const PJArgs<T> &a) {
@@ -4650,8 +4653,8 @@ static int residual_restrict(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc,
     hipStream_t s = S(c, stream);
     // register / shuffle form (k_rrrow) on row shapes; MGK_TUNE_LDS_TILE forces the LDS-tile form
     const RowForm form = row_shape_ok<T>(gf) ? row_form() : ROW_NONE;
-    if (form == ROW_DPP || form == ROW_PRED_DPP) launch_rrrow<T, 1, 2>(w, nblk, s, a);      // DPP lane shifts
-    else if (form != ROW_NONE) launch_rrrow<T, 1, 0>(w, nblk, s, a);
+    if (form == ROW_DPP || form == ROW_PRED_DPP) launch_rrrow<T, 1, 2>(w, nblk, s, a, exact_fma7(coef));      // DPP lane shifts
+    else if (form != ROW_NONE) launch_rrrow<T, 1, 0>(w, nblk, s, a, false);
     else LAUNCH_WX(width_1248, w, (k_resrestrict<T, WX>), nblk, s, a);
     HIPCHK(hipGetLastError());
     return 0;

@@ -393,7 +393,8 @@ struct J33Args {
     double a0, a1, a2, a3, a4, a5, a6, dinv, scale;
     double *partials;
 };
-template <int TY, bool NORM, int g_form>
+// EX: the six off-diagonal terms are exact fused multiply-adds (madd, mgk_dev.hpp)
+template <int TY, bool NORM, int g_form, bool EX>
 __global__ void __launch_bounds__(256, 1) k_jacobi3_3d(const J33Args a) {
     constexpr int R0 = TY + 6, R1 = TY + 4, R2 = TY + 2;
     using VT = V16<double>;
@@ -443,12 +444,12 @@ __global__ void __launch_bounds__(256, 1) k_jacobi3_3d(const J33Args a) {
             const double wv = (e == 0) ? Wv : c.v[0];
             const double ev = (e == 1) ? Ev : c.v[1];
             double s = a.a0 * dn.v[e];
-            s = s + a.a1 * sv.v[e];
-            s = s + a.a2 * wv;
+            s = madd<EX>(s, a.a1, sv.v[e]);
+            s = madd<EX>(s, a.a2, wv);
             s = s + a.a3 * c.v[e];
-            s = s + a.a4 * ev;
-            s = s + a.a5 * nv.v[e];
-            s = s + a.a6 * upv.v[e];
+            s = madd<EX>(s, a.a4, ev);
+            s = madd<EX>(s, a.a5, nv.v[e]);
+            s = madd<EX>(s, a.a6, upv.v[e]);
             const double res = bb.v[e] - s;
             const double zz = res * a.dinv;
             const double val = c.v[e] + a.scale * zz;
@@ -476,12 +477,12 @@ __global__ void __launch_bounds__(256, 1) k_jacobi3_3d(const J33Args a) {
         double s_[NR][2], w_[NR], e_[NR];                                                                              \
         _Pragma("unroll") for (int q = 0; q < NR; q++) { w_[q] = lane_up<true>(C[q + 1].v[1]); e_[q] = lane_dn<true>(C[q + 1].v[0]); } \
         _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = a.a0 * DN[q + o_dn].v[0]; s_[q][1] = a.a0 * DN[q + o_dn].v[1]; } \
-        _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = s_[q][0] + a.a1 * C[q].v[0]; s_[q][1] = s_[q][1] + a.a1 * C[q].v[1]; } \
-        _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = s_[q][0] + a.a2 * w_[q]; s_[q][1] = s_[q][1] + a.a2 * C[q + 1].v[0]; } \
+        _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = madd<EX>(s_[q][0], a.a1, C[q].v[0]); s_[q][1] = madd<EX>(s_[q][1], a.a1, C[q].v[1]); } \
+        _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = madd<EX>(s_[q][0], a.a2, w_[q]); s_[q][1] = madd<EX>(s_[q][1], a.a2, C[q + 1].v[0]); } \
         _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = s_[q][0] + a.a3 * C[q + 1].v[0]; s_[q][1] = s_[q][1] + a.a3 * C[q + 1].v[1]; } \
-        _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = s_[q][0] + a.a4 * C[q + 1].v[1]; s_[q][1] = s_[q][1] + a.a4 * e_[q]; } \
-        _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = s_[q][0] + a.a5 * C[q + 2].v[0]; s_[q][1] = s_[q][1] + a.a5 * C[q + 2].v[1]; } \
-        _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = s_[q][0] + a.a6 * UP[q + o_up].v[0]; s_[q][1] = s_[q][1] + a.a6 * UP[q + o_up].v[1]; } \
+        _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = madd<EX>(s_[q][0], a.a4, C[q + 1].v[1]); s_[q][1] = madd<EX>(s_[q][1], a.a4, e_[q]); } \
+        _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = madd<EX>(s_[q][0], a.a5, C[q + 2].v[0]); s_[q][1] = madd<EX>(s_[q][1], a.a5, C[q + 2].v[1]); } \
+        _Pragma("unroll") for (int q = 0; q < NR; q++) { s_[q][0] = madd<EX>(s_[q][0], a.a6, UP[q + o_up].v[0]); s_[q][1] = madd<EX>(s_[q][1], a.a6, UP[q + o_up].v[1]); } \
         _Pragma("unroll") for (int q = 0; q < NR; q++) {                                                               \
             const double r0_ = BB[q + o_b].v[0] - s_[q][0], r1_ = BB[q + o_b].v[1] - s_[q][1];                          \
             const double z0_ = r0_ * a.dinv, z1_ = r1_ * a.dinv;                                                       \
@@ -569,7 +570,7 @@ __global__ void __launch_bounds__(256, 1) k_jacobi3_3d(const J33Args a) {
 #undef J33_STAGE
 }
 template <int TY, bool NORM>
-static int jacobi3_3d_launch(mgk_ctx *c, J33Args &a, const mgk_geom *g, int *norm_parts, void *stream) {
+static int jacobi3_3d_launch(mgk_ctx *c, J33Args &a, const mgk_geom *g, const double *ex_coef, int *norm_parts, void *stream) {
     a.ntx = ((g->nx + 1) / 2 + 59) / 60;
     a.nty = (g->ny + TY - 1) / TY;
     // one wave per SIMD: 1024 run at a time; cut z so that the wave tiles are a whole number of rounds (>= 4), chunks of >= 32 planes
@@ -589,8 +590,10 @@ static int jacobi3_3d_launch(mgk_ctx *c, J33Args &a, const mgk_geom *g, int *nor
         a.partials = c->partials;
         *norm_parts = (int)(4 * nblk);
     }
-    if (g_variant == MGK_TUNE_J3_3D_ROWWISE) hipLaunchKernelGGL((k_jacobi3_3d<TY, NORM, 0>), dim3(nblk), dim3(256), 0, S(c, stream), a);      // row by row
-    else hipLaunchKernelGGL((k_jacobi3_3d<TY, NORM, 1>), dim3(nblk), dim3(256), 0, S(c, stream), a);                       // term by term over the rows
+    // (the row-by-row form keeps the generic arithmetic: it is a tuning variant, and so is MGK_TUNE_NO_EXACT_FMA -- one variant at a time)
+    if (g_variant == MGK_TUNE_J3_3D_ROWWISE) hipLaunchKernelGGL((k_jacobi3_3d<TY, NORM, 0, false>), dim3(nblk), dim3(256), 0, S(c, stream), a);      // row by row
+    else if (exact_fma7(ex_coef)) hipLaunchKernelGGL((k_jacobi3_3d<TY, NORM, 1, true>), dim3(nblk), dim3(256), 0, S(c, stream), a);   // exact FMA
+    else hipLaunchKernelGGL((k_jacobi3_3d<TY, NORM, 1, false>), dim3(nblk), dim3(256), 0, S(c, stream), a);                // term by term over the rows
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -606,9 +609,10 @@ static int jacobi3_3d(mgk_ctx *c, const mgk_geom *g, const double *coef, double 
     // rows per wave tile: 4 (480-498 registers per lane, none in scratch); with the norm 3 (456): the 4-row form would spill 28-38 registers
     // to scratch.  MGK_TUNE_J3_3D_TY2 / _TY3 force 2 / 3 rows
     const int ty = (g_variant == MGK_TUNE_J3_3D_TY2) ? 2 : (g_variant == MGK_TUNE_J3_3D_TY3 || NORM) ? 3 : 4;
-    if (ty == 2) return jacobi3_3d_launch<2, NORM>(c, a, g, norm_parts, stream);
-    if (ty == 3) return jacobi3_3d_launch<3, NORM>(c, a, g, norm_parts, stream);
-    return jacobi3_3d_launch<4, NORM>(c, a, g, norm_parts, stream);
+    if (ty == 2) return jacobi3_3d_launch<2, NORM>(c, a, g, coef, norm_parts, stream);
+    if (ty == 3) return jacobi3_3d_launch<3, NORM>(c, a, g, coef, norm_parts, stream);
+    if constexpr (!NORM) return jacobi3_3d_launch<4, NORM>(c, a, g, coef, norm_parts, stream);      // (not built with a norm: it would spill)
+    else return fail(MGK_EINVAL, "mgk_jacobi3_sumsq_f64: tile height not built");
 }
 extern "C" int mgk_jacobi3_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                                const double *b, const double *u, double *unew, void *stream) {

@@ -3,6 +3,7 @@
 // coefficients of the argument structs.  Host code only: nothing in here changes what a kernel computes.
 #pragma once
 #include <type_traits>
+#include "mgk_pow2.h"
 
 // ---- wave width: the runtime number of waves per row `w` picks the compile-time WX among WXS (ascending): the first one with w <= WX, the
 // last one for anything wider.  f is called with std::integral_constant<int, WX>.  The instantiations are those of the listed widths only.
@@ -65,3 +66,21 @@ template <typename A> static inline void set_coef5(A &a, const double *coef) {
     typedef decltype(a.a0) T;
     a.a0 = (T)coef[0]; a.a2 = (T)coef[1]; a.a3 = (T)coef[2]; a.a4 = (T)coef[3]; a.a6 = (T)coef[4];
 }
+
+// ---- the exact-FMA form of the fp64 3-D constant-coefficient kernels (madd<true>, mgk_dev.hpp): taken when ALL six off-diagonal coefficients
+// {k-1, i-1, j-1, j+1, i+1, k+1} are +-2^e, e >= 0 (mgk_pow2.h) -- every level of a uniform grid with npts = 2^k + 1 -- unless
+// MGK_TUNE_NO_EXACT_FMA asks for the generic form.  Two instances per kernel, not one per mask.  The results are the same doubles either way.
+// Offered by the kernels where it measured no slower (k_jacobi3_3d, k_jacobi2r, k_pj2r3, k_rrrow: DESIGN.md section 4 (xix)).
+static inline bool exact_fma7(const double *coef) {
+    return g_variant != MGK_TUNE_NO_EXACT_FMA && coef && (mgk_coef_exact_mask(coef, 7) & 0x77u) == 0x77u;
+}
+// LAUNCH_WX with the kernel's last template argument EX chosen by `ex`; `kernel` names WX and EX.  T: the element type -- the exact form is
+// built for double only (inside a template on T the fp32 launchers instantiate nothing new)
+#define LAUNCH_WX_EX(pick, w, T, ex, kernel, nblk, s, ...)                                            \
+    do {                                                                                              \
+        bool done_ = false;                                                                           \
+        if constexpr (sizeof(T) == 8) {                                                               \
+            if (ex) { constexpr bool EX = true; LAUNCH_WX(pick, w, kernel, nblk, s, __VA_ARGS__); done_ = true; } \
+        }                                                                                             \
+        if (!done_) { constexpr bool EX = false; LAUNCH_WX(pick, w, kernel, nblk, s, __VA_ARGS__); }  \
+    } while (0)

@@ -52,6 +52,7 @@ class Tune(enum.IntEnum):
     J3_3D_TY2 = 62
     J3_3D_TY3 = 63
     J3_3D_ROWWISE = 64
+    NO_EXACT_FMA = 65
 
 
 @contextlib.contextmanager
