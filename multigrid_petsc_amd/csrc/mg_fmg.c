@@ -107,7 +107,18 @@ static int fmg_run(mg_solver *s, int nu) {
     CHK(interpolate(s, 0));
     for (int l = 1; l < levels; l++) {                                  /* their contents are spent: back to the recorded buffer roles */
         mg_fset *F = &s->L[l].f[0];
+        /* needed for the RESULT, not for speed alone: the re-record check of cycle_body watches the level that feeds the recording, not the
+         * levels inside it.  A stage level can swap u / tmp an odd number of times (the root's first pre-smoothing is shortened by pre_done,
+         * the post-smoothing is not); a recording made by an earlier cycle then leaves level lgraph's result in the buffer that was u when it
+         * was recorded, while the prolongation to the level above reads the one that is u now.  Seen with the tail off, the graph on and a
+         * second FMG on a live handle (tools/stress_sessions_mock.py; the fixed sessions of tests/san_fmg.c) */
         if (F->u != u_at[l]) { void *t = F->u; F->u = F->tmp; F->tmp = t; }
+        /* a guard, not a repair: every flag is 0 already.  guess_nonzero: the stage loop above for the stage roots, mgi_vcycle_rooted for the levels
+         * below a root, mgi_start for the tail levels and the coarsest one.  jz_ready is set by a restriction and consumed by the smoothing
+         * (or the tail kernel) that follows it in the same descent; last_sweep_pending is set by a pre-smoothing and consumed by the
+         * restriction that follows it; pre_done is set by interpolate() and consumed by the first smoothing of the nu >= 1 cycles of that
+         * stage.  No session can tell this line from its absence while every stage ends on a complete cycle; it stays so that a stage
+         * that does not (nu = 0, an early exit) cannot leak a flag into the solver's own cycles, where a stale jz_ready skips a sweep */
         F->guess_nonzero = 0; F->jz_ready = 0; F->last_sweep_pending = 0; F->pre_done = 0;
     }
     s->last_cycle = 0;

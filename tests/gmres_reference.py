@@ -143,3 +143,24 @@ def delta(a, b):
 def distance(x, rnorm, ref):
     """the same two quantities between a result (x, rnorm) and one variant of the reference"""
     return delta({"x": np.asarray(x), "rnorm": np.asarray(rnorm)}, ref)
+
+
+def judge(orc, config, b, refs, it, rn, x, bnorm, rtol=1.0e-7):
+    """The bars a solve_gmres result (it, rn, x, bnorm) is held to, on config = (dim, npts, levels, mesh, scale) and the right-hand side b,
+    against refs = the reference's two orders of summation (dot="np", "ld"): a stop decision clear of rounding in both, the same count, the
+    history's length and its first entry, x and the history within 100 delta of the nearer variant (delta = the distance between the two,
+    floor 1e-13), and a converged TRUE residual.  Shared by tests/test_gmres_cpu.py and the session draw (tools/stress_sessions_mock.py)."""
+    dim, npts, levels, mesh, scale = config
+    for r in refs:
+        last, before = margins(r, rtol)
+        assert last <= 0.8 and before >= 1.5, (last, before)
+    assert it == refs[0]["iters"] == refs[1]["iters"]
+    assert len(rn) == it + 1 and rn[0] == bnorm and abs(bnorm - refs[0]["bnorm"]) <= 1e-13 * bnorm
+    bound = max(100.0 * delta(refs[0], refs[1]), 1e-13)
+    dist = min(distance(x, rn, r) for r in refs)
+    assert dist <= bound, (dist, bound)
+    op = Operators(orc, dim, npts, levels, mesh, scale)
+    r = b - op.A(x)
+    op.close()
+    eps = max(abs(q["rnorm"][-1] - q["true"]) / q["true"] for q in refs)
+    assert np.sqrt(np.dot(r, r)) <= rtol * bnorm * (1.0 + 100.0 * eps)

@@ -6,6 +6,8 @@
 // kernel touches (ghost rows / planes, far planes included), in the canonical arithmetic of DESIGN.md section 2, so a wrong
 // geometry, pointer or plane count in the host code is an ASan report, and results can be compared with the oracle.
 // NOT a CPU fallback: it is never built into, linked with or loaded by anything under multigrid_petsc_amd/.
+#ifndef MOCK_MGK_CPP        // (tests/mock_mgk_sessions_line.cpp includes two of the chains of stand-ins that include this file)
+#define MOCK_MGK_CPP
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1028,3 +1030,4 @@ int mgk_correct_residual_f64_f32_jz(mgk_ctx *c, const mgk_geom *g, const mgk_geo
     return rc;
 }
 }   // extern "C"
+#endif

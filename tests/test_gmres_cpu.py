@@ -96,19 +96,7 @@ def _compare(orc, case, it, rn, x, bnorm):
     """the bars of the GPU tier on a result of the product's host code"""
     dim, npts, levels, mesh, scale, restart, rhs, maxiter = case
     b, refs = _reference(orc, case)
-    for r in refs:
-        last, before = G.margins(r, RTOL)
-        assert last <= 0.8 and before >= 1.5, (last, before)
-    assert it == refs[0]["iters"] == refs[1]["iters"]
-    assert len(rn) == it + 1 and rn[0] == bnorm and abs(bnorm - refs[0]["bnorm"]) <= 1e-13 * bnorm
-    bound = max(100.0 * G.delta(refs[0], refs[1]), 1e-13)
-    dist = min(G.distance(x, rn, r) for r in refs)
-    assert dist <= bound, (dist, bound)
-    op = G.Operators(orc, dim, npts, levels, mesh, scale)
-    r = b - op.A(x)
-    op.close()
-    eps = max(abs(q["rnorm"][-1] - q["true"]) / q["true"] for q in refs)
-    assert np.sqrt(np.dot(r, r)) <= RTOL * bnorm * (1.0 + 100.0 * eps)
+    G.judge(orc, (dim, npts, levels, mesh, scale), b, refs, it, rn, x, bnorm, RTOL)      # (the bars themselves: shared with the session draw)
     return refs
 
 
