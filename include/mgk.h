@@ -586,6 +586,21 @@ int  mgk_xline_forward_f64(mgk_ctx *ctx, const mgk_geom *g, const double *atab, 
 int  mgk_xline_backward_f64(mgk_ctx *ctx, const mgk_geom *g, const double *atab, const double *gtab, long gstride, double scale,
                             const double *z, const double *u, double *unew, void *stream);
 
+/* ---- the LDS-resident coarse levels of a line cycle in one launch (csrc/mg_line_tail.c; kernel in csrc/mgk_line_tail.hip) ----
+ * The contract of mgk_tail_cycle_f64 with line sweeps as the smoother: one workgroup of 1024 lanes keeps u, z and b of the `nlev` levels
+ * (n[0] <= mgk_tail_max_n(2), n[l-1] = 2 n[l] + 1, 1 <= nlev <= 8, 2-D) in LDS and runs src/solver.c:1533-1544 on them -- b of the first
+ * tail level (padded field of geometry g0) comes in, its u after the post-smoothing goes out -- bit-identical to the launch-by-launch loop
+ * over mgk_line_* / mgk_xline_* (above), the row-table residual, mgk_restrict_fw_f64 and mgk_prolong_add_f64.  pc: 1 y-line, 2 x-line,
+ * 3 alternating (mg_pc_type's MG_PC_LINE_Y / _X / _ALT): sweep k of every smoothing, counted from 0, is an x sweep under 2 and for odd k
+ * under 3 -- the coarsest level's v1 sweeps too.  Device tables per level: atab (n[l] x 5, {S, W, C, E, N} per grid row, as mgk_line_* and
+ * mgk_xline_* take it -- the ctab of mgk_tail_cycle_rowcoef_f64); ltab / gtab /
+ * qtab (n[l] each, as mgk_line_*; may be NULL with pc 2); xgtab with its row stride xgs[l] (0: one row; as mgk_xline_*; may be NULL with
+ * pc 1).  An x table with rows is read from global memory and must not change while the kernel runs.  Anything else: MGK_EINVAL. */
+int  mgk_tail_cycle_line_f64(mgk_ctx *ctx, const mgk_geom *g0, int nlev, const int *n, int pc, const double *const *atab,
+                             const double *const *ltab, const double *const *gtab, const double *const *qtab,
+                             const double *const *xgtab, const long *xgs,
+                             double scale, int v0, int v1, const double *b, double *u, void *stream);
+
 /* ---- the y-line sweep in chunks (csrc/mg_line_chunk.c; kernels in csrc/mgk_line_chunk.hip) ----
  * The sweep of mgk_line_forward_f64 / mgk_line_backward_f64 with the tridiagonal systems partitioned: period c >= 2, K = ny / c, row
  * s_j = j c + c - 1 is separator j, the rows [k c, min(k c + c - 1, ny)) are chunk k (0 <= k <= K), solved independently of each other; the

@@ -120,6 +120,15 @@ typedef struct mg_config {
                          * y-line sweep for even k and an x-line sweep for odd k -- the same number of sweeps as MG_PC_LINE_Y, and a cycle count
                          * independent of npts on meshes 0, 1 and 2.  Both under the conditions of MG_PC_LINE_Y, with
                          * the same refusals */
+    int line_tail;      /* (0, default: off) 1: the coarse levels of a line cycle (MG_PC_LINE_Y / _X / _ALT) whose fields fit in LDS run as ONE
+                         * kernel per cycle (mgk_tail_cycle_line_f64) instead of two launches per sweep plus the
+                         * transfers -- what fuse bit 9 is to point Jacobi.  Bit-identical to the launches it replaces.  The tail starts at
+                         * the first level l >= 1 with n <= 63 that is also below every chunk period that applies (n < line_chunk where
+                         * the pc has y sweeps, n < xline_chunk where it has x sweeps: the kernel makes plain sweeps only); it needs 2 to 8
+                         * such levels and v0 >= 1, otherwise 1 is accepted and the tail stays off (mg_solver_tail_level tells).
+                         * Independent of `fuse`: bit 9 stays cleared for the line smoothers, and fuse = 0 with line_tail = 1 still uses the
+                         * tail.  Any other value, or 1 with MG_PC_JACOBI: MGK_EINVAL.  (The two chunk periods stay the last
+                         * fields of the struct: new options go before them) */
     int xline_chunk;    /* (0, default: off) c > 0, a multiple of 16: every x-line sweep (MG_PC_LINE_X, the odd sweeps of MG_PC_LINE_ALT) solves its
                          * tridiagonal systems in chunks of c columns -- column q c + c - 1 is a separator, the c - 1 columns before it a
                          * chunk; the chunks are solved independently, the n / c separators of a row by their Schur complement, the chunks
@@ -189,6 +198,9 @@ const double *mg_solver_rnorm(const mg_solver *s);
 double mg_solver_solve_seconds(const mg_solver *s);       /* "Solver walltime" window (src/solver.c:1526,1553) */
 
 int  mg_solver_num_levels(const mg_solver *s);
+/* the first level that runs inside a tail kernel (fuse bit 9, or line_tail with a line smoother): it and every coarser level are one launch
+ * per cycle, their fields in LDS; 0: none */
+int  mg_solver_tail_level(const mg_solver *s);
 int  mg_solver_level_n(const mg_solver *s, int level);              /* unknowns per side */
 int  mg_solver_level_local_planes(const mg_solver *s, int level, int *z0);
 long mg_solver_local_unknowns(const mg_solver *s);

@@ -91,6 +91,7 @@ int main(int argc, char **argv) {
         return 2;
     }
     if ((v = get("-xline_chunk"))) c.xline_chunk = atoi(v);                         /* the x-line sweeps in chunks of that many columns (0: whole) */
+    if ((v = get("-line_tail"))) c.line_tail = atoi(v);                             /* 1: the LDS-resident coarse levels of a line cycle in one launch */
     if ((v = get("-line_chunk"))) c.line_chunk = atoi(v);                           /* the y-line sweeps in chunks of that many rows (0: whole) */
     if ((v = get("-cycle")) && atoi(v) != 0) { fprintf(stderr, "mgpoisson: only -cycle 0 (V-cycle) is built\n"); return 2; }
     if ((v = get("-mesh"))) c.mesh = atoi(v);

@@ -253,6 +253,7 @@ void mg_config_default(mg_config *c) {
     c->slab_chunk = -1;
     c->xline_chunk = 0;                          /* the x-line sweeps whole (mg_xline.c) */
     c->line_chunk = 0;                           /* the y-line sweeps whole (mg_line.c) */
+    c->line_tail = 0;                            /* the coarse levels of a line cycle by launch (1: one kernel, mg_line_tail.c) */
 }
 
 static int alloc_fset(mg_solver *s, mg_fset *F, int esz, int all4) {
@@ -333,6 +334,12 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         return mgfail(MGK_EINVAL, "mg_solver_create: xline_chunk splits x-line sweeps: it needs pc_type xline or altline (not jacobi or yline)");
     if (cfg->xline_chunk > 0 && (!mg_xline_chunk_tables || !mg_xline_chunk_smooth))
         return mgfail(MGK_EINVAL, "mg_solver_create: this build has no chunked x-line sweep (mg_xline_chunk.c is not linked)");
+    if (cfg->line_tail != 0 && cfg->line_tail != 1)
+        return mgfail(MGK_EINVAL, "mg_solver_create: line_tail must be 0 (off) or 1 (on)");
+    if (cfg->line_tail == 1 && cfg->pc_type == MG_PC_JACOBI)
+        return mgfail(MGK_EINVAL, "mg_solver_create: line_tail goes with the line smoothers (pc_type yline, xline or altline; point Jacobi has fuse bit 9)");
+    if (cfg->line_tail == 1 && !mg_line_tail)
+        return mgfail(MGK_EINVAL, "mg_solver_create: this build has no one-launch tail of the line cycles (mg_line_tail.c is not linked)");
     if (cfg->precision == MG_PREC_MIXED && (cfg->dim != 3 || cfg->ksp_type != MG_KSP_RICHARDSON))
         return mgfail(MGK_EINVAL, "mg_solver_create: mixed precision is built for 3-D, Richardson+Jacobi");
     /* npts-1 must be divisible by 2^(levels-1) and the coarsest grid must keep >= 1 unknown */
@@ -461,6 +468,17 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
     if ((s->cfg.fuse & MG_FUSE_LDS_TAIL) && ((s->cfg.ksp_type == MG_KSP_RICHARDSON && s->cfg.v[0] >= 1) || cheby_tail)) {
         for (int l = (s->ldist > 0 ? s->ldist : 1); l < s->levels; l++)
             if (s->L[l].n <= mgk_tail_max_n(cfg->dim)) { s->ltail = l; break; }
+        if (s->ltail && (s->levels - s->ltail < 2 || s->levels - s->ltail > 8)) s->ltail = 0;
+    }
+    /* line smoothers (fuse bit 9 is cleared for them): mg_config.line_tail, whatever `fuse` says.  The kernel makes PLAIN sweeps only and a
+     * chunked sweep rounds differently, so the tail starts below every chunk period that applies to this pc_type (n falls with l: once a
+     * level qualifies, all below it do).  As for bit 9: 2 to 8 levels and v0 >= 1, else the tail stays off */
+    if (s->cfg.line_tail && s->cfg.pc_type != MG_PC_JACOBI && s->cfg.v[0] >= 1 && s->cfg.v[1] >= 0) {
+        const int yc = (s->cfg.pc_type != MG_PC_LINE_X) ? s->cfg.line_chunk : 0, xc = (s->cfg.pc_type != MG_PC_LINE_Y) ? s->cfg.xline_chunk : 0;
+        for (int l = 1; l < s->levels; l++) {
+            const int n = s->L[l].n;
+            if (n <= mgk_tail_max_n(2) && (yc <= 0 || n < yc) && (xc <= 0 || n < xc)) { s->ltail = l; break; }
+        }
         if (s->ltail && (s->levels - s->ltail < 2 || s->levels - s->ltail > 8)) s->ltail = 0;
     }
     if (s->cfg.graph) {
@@ -1221,6 +1239,11 @@ static int tail(mg_solver *s, int P) {
         for (int e = 0; e < 7; e++) k7[7 * q + e] = L->coef[e];
     }
     mg_fset *F = &s->L[lt].f[P];
+    if (s->cfg.pc_type != MG_PC_JACOBI) {         /* mg_config.line_tail: the line sweeps of those levels in one kernel (mg_line_tail.c) */
+        CHK(mg_line_tail(s));
+        F->jz_ready = 0;
+        return 0;
+    }
     if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV) {
         CHK(mg_cheby_tail(s));
         F->jz_ready = 0;
@@ -1739,6 +1762,7 @@ double mg_solver_bnorm(const mg_solver *s) { return s->bnorm; }
 const double *mg_solver_rnorm(const mg_solver *s) { return s->rnorm; }
 double mg_solver_solve_seconds(const mg_solver *s) { return s->solve_seconds; }
 int mg_solver_num_levels(const mg_solver *s) { return s->levels; }
+int mg_solver_tail_level(const mg_solver *s) { return s ? s->ltail : 0; }
 int mg_solver_level_n(const mg_solver *s, int l) { return (l >= 0 && l < s->levels) ? s->L[l].n : -1; }
 int mg_solver_level_local_planes(const mg_solver *s, int l, int *z0) {
     if (l < 0 || l >= s->levels) return -1;

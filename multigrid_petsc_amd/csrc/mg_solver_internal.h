@@ -87,7 +87,8 @@ struct mg_solver {
                              * tmp holds the sweep after it); finalize_iterate() makes the sweep if the iteration stops here */
     double solve_seconds;
     int lgraph;             /* levels >= lgraph form the launch-bound coarse part replayed as one HIP graph (0: off) */
-    int ltail;              /* levels >= ltail (n <= 15 in 3-D, <= 63 in 2-D) run as ONE kernel with their fields in LDS (0: off) */
+    int ltail;              /* levels >= ltail (n <= 15 in 3-D, <= 63 in 2-D) run as ONE kernel with their fields in LDS (0: off); line smoothers:
+                             * mg_config.line_tail, below every chunk period that applies */
     void *coarse_graph[2];  /* one recording per precision */
     void *graph_u[2], *graph_tmp[2];   /* u / tmp of the level that feeds the recording, as the recorded kernels know them */
     int graph_rerecorded;   /* recordings thrown away because those pointers had changed (0 in every default configuration) */
@@ -132,6 +133,10 @@ extern int mg_line_chunk_smooth(mg_solver *s, int l, int maxit) __attribute__((w
  * xline_chunk > 0 in a build without it */
 extern int mg_xline_chunk_tables(mg_solver *s, int l, const double *ctab_host) __attribute__((weak));  /* level l's tables; none when n < c */
 extern int mg_xline_chunk_smooth(mg_solver *s, int l, int maxit) __attribute__((weak));  /* maxit x sweeps on a level with chunk tables */
+/* the LDS-resident coarse levels of a line cycle in one launch (mg_config.line_tail = 1): mg_line_tail.c holds the only call of
+ * mgk_tail_cycle_line_f64; mg_solver.c (tail()) reaches it through a WEAK reference, and mg_solver_create refuses line_tail = 1 in a build
+ * without it */
+extern int mg_line_tail(mg_solver *s) __attribute__((weak));      /* the levels ltail .. L-1 of one cycle in one kernel */
 long mg_xline_stride(int n, int uniform);                                          /* row stride of the x table (mg_xline.c) */
 void mg_xline_factor(int n, int rows, const double *ctab, long gs, double *g);     /* the x table on the host (mg_xline.c) */
 

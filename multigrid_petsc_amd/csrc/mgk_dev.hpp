@@ -41,6 +41,7 @@ int mgk_preload_line();          // ... and that of mgk_line.hip
 int mgk_preload_xline();         // ... and that of mgk_xline.hip
 int mgk_preload_line_chunk();    // ... and that of mgk_line_chunk.hip
 int mgk_preload_xline_chunk();   // ... and that of mgk_xline_chunk.hip
+int mgk_preload_line_tail();     // ... and that of mgk_line_tail.hip
 #include "mgk_launch.hpp"        // the launch rules of the host side (they read the context and the knobs above)
 #define MGK_RESULT_SLOTS 64      // >= MGK_KRYLOV_MAX + 1: the dots of an Arnoldi step and the norm that follows them
 

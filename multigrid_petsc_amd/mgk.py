@@ -243,6 +243,9 @@ def _sigs(L):
         "mgk_xline_chunk_backward_f64": (i, [vp, G, i, vp, vp, C.c_long, vp, vp, vp]),
         "mgk_xline_chunk_reduce_f64": (i, [vp, G, i, vp, vp, vp, vp, C.c_long, vp, vp]),
         "mgk_xline_chunk_correct_f64": (i, [vp, G, i, vp, vp, C.c_long, d, vp, vp, vp, vp, vp]),
+        # the LDS-resident coarse levels of a line cycle in one launch: (nlev, n, pc, ctab[], ltab[], gtab[], qtab[], xgtab[], xgs[], scale, v0, v1, b, u)
+        "mgk_tail_cycle_line_f64": (i, [vp, G, i, C.POINTER(i), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                        C.POINTER(C.c_long), d, i, i, vp, vp, vp]),
     }
     for name, (res, args) in S.items():
         f = getattr(L, name)
@@ -345,6 +348,19 @@ class Mgk:
     def raw_field(self, g, f):
         """whole padded allocation (ghosts included) as a flat numpy array"""
         return self.download(f, g.total)
+
+    def tail_cycle_line(self, g0, n, pc, ctab, ltab=None, gtab=None, qtab=None, xgtab=None, xgs=None, scale=1.0, v=(3, 3), b=None, u=None):
+        """mgk_tail_cycle_line_f64: the levels n[0] > n[1] > ... of a line cycle in one launch, b of the first level in, its u out (padded
+        device fields of geometry g0).  pc: 1 y-line, 2 x-line, 3 alternating.  The tables are lists of device pointers, one per level
+        (None: the argument is passed as NULL); xgs the row strides of the x tables.  Returns the kernel ABI's return code"""
+        nl = len(n)
+
+        def ptrs(tabs):
+            return None if tabs is None else (C.c_void_p * nl)(*[t if isinstance(t, C.c_void_p) else C.c_void_p(t) for t in tabs])
+
+        strides = None if xgs is None else (C.c_long * nl)(*xgs)
+        return self.L.mgk_tail_cycle_line_f64(self.ctx, C.byref(g0), nl, (C.c_int * nl)(*n), pc, ptrs(ctab), ptrs(ltab), ptrs(gtab), ptrs(qtab),
+                                              ptrs(xgtab), strides, scale, v[0], v[1], b, u, None)
 
     @staticmethod
     def coef(vals):

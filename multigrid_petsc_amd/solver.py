@@ -18,7 +18,7 @@ class MgConfig(C.Structure):
                 ("device", C.c_int), ("precision", C.c_int), ("rank", C.c_int), ("nranks", C.c_int),
                 ("dist_min_n", C.c_int), ("fuse", C.c_int), ("overlap", C.c_int), ("graph", C.c_int),
                 ("pair_min_n", C.c_int), ("slab_chunk", C.c_int), ("mesh", C.c_int), ("pc_type", C.c_int),
-                ("xline_chunk", C.c_int), ("line_chunk", C.c_int)]
+                ("line_tail", C.c_int), ("xline_chunk", C.c_int), ("line_chunk", C.c_int)]
 
 
 class MgError(RuntimeError):
@@ -78,6 +78,8 @@ def _lib():
     L.mg_solver_solve_seconds.argtypes = [vp]
     L.mg_solver_num_levels.restype = i
     L.mg_solver_num_levels.argtypes = [vp]
+    L.mg_solver_tail_level.restype = i
+    L.mg_solver_tail_level.argtypes = [vp]
     L.mg_solver_level_n.restype = i
     L.mg_solver_level_n.argtypes = [vp, i]
     L.mg_solver_level_local_planes.restype = i
@@ -147,7 +149,7 @@ class Solver:
     def __init__(self, dim, npts, levels, v=(3, 3), maxiter=100000, ksp_type="richardson", scale=1.0,
                  eigenvalues=(0.0, 0.0), rtol=1.0e-7, device=0, rank=0, nranks=1, comm=None,
                  dist_min_n=0, fuse=-1, overlap=-1, precision="fp64", graph=-1, pair_min_n=0, mesh=0, slab_chunk=-1, pc_type="jacobi",
-                 line_chunk=0, xline_chunk=0):
+                 line_chunk=0, xline_chunk=0, line_tail=0):
         self.L = _lib()
         cfg = MgConfig()
         self.L.mg_config_default(C.byref(cfg))
@@ -167,6 +169,7 @@ class Solver:
         cfg.pc_type = _PC[pc_type]        # "yline" / "xline": y- / x-line Jacobi, "altline": y and x sweeps in turn (2-D, fp64, one rank, Richardson; include/mgsolve.h)
         cfg.xline_chunk = xline_chunk     # c > 0, a multiple of 16: the x-line sweeps in chunks of c columns (four passes per sweep); 0: whole
         cfg.line_chunk = line_chunk       # c >= 2: the y-line sweeps in chunks of c rows (four passes per sweep); 0: whole
+        cfg.line_tail = line_tail         # 1: the LDS-resident coarse levels of a line cycle in one launch; 0: by launch
         self.cfg = cfg
         self.h = C.c_void_p()
         self._chk(self.L.mg_solver_create(C.byref(self.h), C.byref(cfg), comm))
@@ -242,6 +245,11 @@ class Solver:
     @property
     def dof_updates_per_cycle(self):
         return self.L.mg_solver_dof_updates_per_cycle(self.h)
+
+    @property
+    def tail_level(self):
+        """the first level that runs inside a tail kernel (fuse bit 9; line_tail for the line smoothers); 0: none"""
+        return self.L.mg_solver_tail_level(self.h)
 
     def level_n(self, l):
         return self.L.mg_solver_level_n(self.h, l)

@@ -3,7 +3,7 @@ V-cycle-preconditioned GMRES over it, one GPU, time to rtol 1e-7 at Richardson s
 between them (drift of the machine hits all alike), after one warm-up of each (first launches, the graph recording, the basis allocation).
 Reported per case: iterations, every sample of solve_seconds, and whether EVERY yline sample lies below EVERY sample of the others.
 
-    python tools/bench_line.py --case 4097:1:30 [--samples 5] [--only yline|altline|xline|jacobi|gmres] [--chunk C] [--xchunk C] [--out FILE]      (run one case per process)
+    python tools/bench_line.py --case 4097:1:30 [--samples 5] [--only yline|altline|xline|jacobi|gmres] [--chunk C] [--xchunk C] [--line-tail 1] [--out FILE]      (run one case per process)
     python tools/bench_line.py --kernels 4095,2047,1023 [--depths 8,16,32] [--xdepths 1,2,3] [--chunk C] [--xchunk C,C,..] [--uniform] [--reps 20] [--out FILE]
 
 A case is npts:mesh[:restart]; with a restart length solve_gmres(restart) on a point-Jacobi solver is the third contender.  --only runs one
@@ -13,7 +13,8 @@ depths and the x : y pass ratio.  --chunk C (line_chunk): 
 rows; with --kernels the four passes of a chunked y sweep are timed as well (under "chunk_<C>": per pass and per sweep the time of 10 launches back to back and one synchronise, over 10; the plain sweep is timed the
 same way under "depth_<D>"/"sweep", beside the plain passes).  --xchunk C (xline_chunk): the xline and altline solvers make
 their x sweeps in chunks of C columns; with --kernels (a list of C is taken) the four passes of a chunked x sweep are timed in the same way under
-"xchunk_<C>", and the plain x sweep of every depth back to back under "xdepth_<D>"/"sweep".  --uniform: the x tables in the stride-0 form of the
+"xchunk_<C>", and the plain x sweep of every depth back to back under "xdepth_<D>"/"sweep".  --line-tail 1 (line_tail): the
+line solvers run the coarse levels that fit in LDS as one kernel per cycle; the row then carries line_tail and every solver's tail_level.  --uniform: the x tables in the stride-0 form of the
 uniform mesh (one row for every grid row)."""
 import argparse
 import ctypes as C
@@ -35,11 +36,12 @@ SCALE = 0.8
 INNER = 10          # --chunk with --kernels: launches per timed sample (a chunked pass is tens of microseconds: one launch + sync would measure the sync)
 
 
-def run(npts, mesh, restart, samples, only, chunk=0, xchunk=0):
+def run(npts, mesh, restart, samples, only, chunk=0, xchunk=0, line_tail=0):
     levels = (npts - 1).bit_length() - 1
     kinds = [only] if only else ["yline", "altline", "jacobi"] + (["gmres"] if restart else [])
+    tail = lambda k: dict(line_tail=1) if line_tail and k in ("yline", "xline", "altline") else {}
     S = {k: Solver(2, npts, levels, v=(3, 3), scale=SCALE, maxiter=2000, rtol=RTOL, mesh=mesh, pc_type="jacobi" if k == "gmres" else k,
-                   line_chunk=chunk if k in ("yline", "altline") else 0, xline_chunk=xchunk if k in ("xline", "altline") else 0)
+                   line_chunk=chunk if k in ("yline", "altline") else 0, xline_chunk=xchunk if k in ("xline", "altline") else 0, **tail(k))
          for k in kinds}
     call = {k: (lambda s: s.solve()) for k in ("yline", "altline", "xline", "jacobi")}
     call["gmres"] = lambda s: s.solve_gmres(restart)
@@ -52,11 +54,14 @@ def run(npts, mesh, restart, samples, only, chunk=0, xchunk=0):
             s.reset()
             its[k] = call[k](s)
             secs[k].append(s.solve_seconds)
-    row = {"npts": npts, "levels": levels, "mesh": mesh, "scale": SCALE, "restart": restart, "rtol": RTOL, "samples": samples, "line_chunk": chunk, "xline_chunk": xchunk}
+    row = {"npts": npts, "levels": levels, "mesh": mesh, "scale": SCALE, "restart": restart, "rtol": RTOL, "samples": samples, "line_chunk": chunk, "xline_chunk": xchunk,
+           "line_tail": line_tail}
     for k, s in S.items():
         rn = s.rnorm
         row[k] = {"iterations": its[k], "converged": bool(rn[-1] <= RTOL * s.bnorm), "relative_residual": float(rn[-1] / rn[0]),
                   "seconds": secs[k], "seconds_median": statistics.median(secs[k])}
+        if line_tail:
+            row[k]["tail_level"] = s.tail_level
         s.close()
     for k in kinds:
         if k != "yline" and "yline" in kinds:
@@ -242,6 +247,8 @@ def main():
     ap.add_argument("--xdepths", default="1,2,3")
     ap.add_argument("--chunk", type=int, default=0, help="line_chunk of the yline / altline solvers; with --kernels: time the four chunked passes too")
     ap.add_argument("--xchunk", default="0", help="xline_chunk of the xline / altline solvers; with --kernels: a list, time the four chunked x passes of each")
+    ap.add_argument("--line-tail", type=int, default=0, choices=[0, 1],
+                    help="--case: 1 = the line solvers run their LDS-resident coarse levels in one launch (mg_config.line_tail, DESIGN.md section 8j)")
     ap.add_argument("--uniform", action="store_true", help="--kernels: the x tables in the stride-0 form of the uniform mesh")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
@@ -253,7 +260,7 @@ def main():
         if "," in a.xchunk:
             ap.error("--case takes one --xchunk value (a list goes with --kernels)")
         f = a.case.split(":")
-        rows = [run(int(f[0]), int(f[1]), int(f[2]) if len(f) > 2 else 0, a.samples, a.only, a.chunk, int(a.xchunk))]
+        rows = [run(int(f[0]), int(f[1]), int(f[2]) if len(f) > 2 else 0, a.samples, a.only, a.chunk, int(a.xchunk), a.line_tail)]
     else:
         ap.error("give --case or --kernels")
     for r in rows:
