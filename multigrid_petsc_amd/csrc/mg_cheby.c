@@ -14,8 +14,6 @@
 #include "mg_solver_internal.h"
 #include <stddef.h>
 
-#define CHK(call) do { int rc_ = (call); if (rc_) return mgi_fail(rc_, #call); } while (0)
-
 /* {s, (1 - w, w, w Gamma s) of step 2, of step 3}: the factors smooth_chebyshev passes to its step-by-step launches (mg_cheby_coefs.h) */
 static void cheb7(const mg_solver *s, double *c) {
     mg_cheby_rec rec;

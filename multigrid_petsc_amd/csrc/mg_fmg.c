@@ -18,8 +18,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#define CHK(call) do { int rc_ = (call); if (rc_) return mgi_fail(rc_, #call); } while (0)
-
 static int fmg_check(const mg_solver *s, int nu) {
     if (!s) return mgi_fail(MGK_EINVAL, "mg_solver_fmg: null solver");
     if (nu < 1) return mgi_fail(MGK_EINVAL, "mg_solver_fmg: nu must be >= 1");

@@ -24,7 +24,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#define CHK(call) do { int rc_ = (call); if (rc_) return mgi_fail(rc_, #call); } while (0)
 #define KM MGK_KRYLOV_MAX
 
 static int gmres_check(const mg_solver *s, int restart) {

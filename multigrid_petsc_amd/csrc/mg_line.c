@@ -9,35 +9,22 @@
  *
  *   m_0 = C_0, g_0 = 1/m_0, l_0 = 0;   i >= 1: l_i = S_i g_{i-1}, m_i = C_i - l_i N_{i-1}, g_i = 1/m_i;   q_i = N_i g_i
  *
+ * (band_factor, mg_line_factor.h, on the bands S, C, N of the row table).
+ *
  * A sweep is a forward pass (residual, forward substitution, z = y g -> the level's tmp) and a backward pass (back substitution and the
  * update, in place in u): no buffer is swapped, so the pointers a recorded coarse-level graph holds stay valid whatever the sweep counts.
  * This file is the only host code that calls the two kernels; mg_solver.c refers to it weakly (mg_solver_internal.h).
  */
 #include "mg_solver_internal.h"
+#include "mg_line_factor.h"
 #include <stdlib.h>
-
-#define CHK(call) do { int rc_ = (call); if (rc_) return mgi_fail(rc_, #call); } while (0)
-
-static void line_factor(int n, const double *ctab, double *lt, double *gt, double *qt) {
-    double m = ctab[2];
-    gt[0] = 1.0 / m;
-    lt[0] = 0.0;
-    for (int i = 1; i < n; i++) {
-        const double *r = ctab + 5 * (size_t)i;
-        lt[i] = r[0] * gt[i - 1];
-        const double t = lt[i] * ctab[5 * (size_t)(i - 1) + 4];
-        m = r[2] - t;
-        gt[i] = 1.0 / m;
-    }
-    for (int i = 0; i < n; i++) qt[i] = ctab[5 * (size_t)i + 4] * gt[i];
-}
 
 int mg_line_tables(mg_solver *s, int l, const double *ctab_host) {
     mg_level *L = &s->L[l];
     const size_t n = (size_t)L->n;
     double *h = (double *)malloc(sizeof(double) * 3 * n);
     if (!h) return mgi_fail(MGK_EINVAL, "mg_line_tables: out of host memory");
-    line_factor(L->n, ctab_host, h, h + n, h + 2 * n);
+    band_factor(L->n, 5, ctab_host, ctab_host + 2, ctab_host + 4, h, h + n, h + 2 * n);
     int rc = mgi_upload(s, h, n, &L->ltab);
     if (!rc) rc = mgi_upload(s, h + n, n, &L->gtab);
     if (!rc) rc = mgi_upload(s, h + 2 * n, n, &L->qtab);

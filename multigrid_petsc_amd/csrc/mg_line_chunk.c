@@ -4,10 +4,10 @@
  * Period c, K = n / c: row s_j = j c + c - 1 is separator j, the rows [k c, min(k c + c - 1, n)) are chunk k (0 <= k <= K; the last one is
  * empty when n = K c).  Tables per level, computed here once (C99 double, no FMA: -ffp-contract=off), one device array [l g q v w | L G Q]:
  *
- *   l, g, q   line_factor of mg_line.c restarted in every chunk (l_a = 0, m_a = C_a), 0 in the separator rows
+ *   l, g, q   band_factor (mg_line_factor.h), mg_line.c's factorisation, restarted in every chunk (l_a = 0, m_a = C_a), 0 in the separator rows
  *   v, w      the spikes T_k^-1 (S_a e_a) and T_k^-1 (N_{b-1} e_{b-1}) of chunk k = [a, b), by the two substitutions of the sweep on that
  *             right-hand side; v = 0 on chunk 0, w = 0 on the last chunk, both 0 in the separator rows (stored zeros: the edge cases are exact)
- *   L, G, Q   line_factor's recurrence on the Schur rows d_j = (C_s - S_s w[s-1]) - N_s v[s+1], sub_j = -(S_s v[s-1]), sup_j = -(N_s w[s+1])
+ *   L, G, Q   band_factor's recurrence on the Schur rows d_j = (C_s - S_s w[s-1]) - N_s v[s+1], sub_j = -(S_s v[s-1]), sup_j = -(N_s w[s+1])
  *             (s = n - 1: d_j = C_s - S_s w[s-1], sup_j = 0)
  *
  * A sweep is four passes (include/mgk.h): forward and backward substitution in every chunk (z, then x' in the level's tmp, the residual r_s
@@ -16,24 +16,8 @@
  * only host code that calls the four kernels; mg_solver.c and mg_line.c refer to it weakly (mg_solver_internal.h).
  */
 #include "mg_solver_internal.h"
+#include "mg_line_factor.h"
 #include <stdlib.h>
-
-#define CHK(call) do { int rc_ = (call); if (rc_) return mgi_fail(rc_, #call); } while (0)
-
-/* line_factor's recurrence on three bands of n entries */
-static void band_factor(int n, const double *sub, const double *dia, const double *sup, double *lt, double *gt, double *qt) {
-    if (n < 1) return;
-    double m = dia[0];
-    gt[0] = 1.0 / m;
-    lt[0] = 0.0;
-    for (int i = 1; i < n; i++) {
-        lt[i] = sub[i] * gt[i - 1];
-        const double t = lt[i] * sup[i - 1];
-        m = dia[i] - t;
-        gt[i] = 1.0 / m;
-    }
-    for (int i = 0; i < n; i++) qt[i] = sup[i] * gt[i];
-}
 
 /* the two substitutions of the sweep on the rows [a, b) of x, in place: r -> x' */
 static void chunk_solve(const double *l, const double *g, const double *q, int a, int b, double *x) {
@@ -66,7 +50,7 @@ int mg_line_chunk_tables(mg_solver *s, int lev, const double *ctab) {
         const int a = k * c, b = (a + c - 1 < n) ? a + c - 1 : n;
         if (b <= a) continue;
         for (int i = a; i < b; i++) { bs[i] = ctab[5 * (size_t)i]; bd[i] = ctab[5 * (size_t)i + 2]; bu[i] = ctab[5 * (size_t)i + 4]; }
-        band_factor(b - a, bs + a, bd + a, bu + a, l + a, g + a, q + a);
+        band_factor(b - a, 1, bs + a, bd + a, bu + a, l + a, g + a, q + a);
         if (k > 0) {
             for (int i = a; i < b; i++) x[i] = 0.0;
             x[a] = bs[a];
@@ -95,7 +79,7 @@ int mg_line_chunk_tables(mg_solver *s, int lev, const double *ctab) {
             sup[j] = -t;
         }
     }
-    band_factor(K, sub, dia, sup, LL, GG, QQ);
+    band_factor(K, 1, sub, dia, sup, LL, GG, QQ);
     const int rc = mgi_upload(s, h, len, &L->chunktab);
     free(h);
     return rc;

@@ -11,8 +11,6 @@
 #include "mg_solver_internal.h"
 #include <stddef.h>
 
-#define CHK(call) do { int rc_ = (call); if (rc_) return mgi_fail(rc_, #call); } while (0)
-
 int mg_line_tail(mg_solver *s) {
     const int lt = s->ltail, nl = s->levels - lt, pc = s->cfg.pc_type;
     int n[8];

@@ -29,7 +29,6 @@ static int mgfail(int code, const char *what) {
     snprintf(g_mgerr, sizeof(g_mgerr), "%s (code %d; kernel layer: %s)", what, code, mgk_last_error());
     return code;
 }
-#define CHK(call) do { int rc_ = (call); if (rc_) return mgfail(rc_, #call); } while (0)
 
 /* the kernel ABI of one precision behind untyped pointers: the cycle code below is written once */
 typedef struct mg_ops {

@@ -142,6 +142,8 @@ void mg_xline_factor(int n, int rows, const double *ctab, long gs, double *g);  
 
 /* the steps of mg_solver.c, for mg_fmg.c (fp64, one rank) */
 int    mgi_fail(int code, const char *what);            /* records the message for mg_last_error(), returns code */
+/* a failed call of the kernel layer ends the calling function with its code, the call's text recorded as the message */
+#define CHK(call) do { int rc_ = (call); if (rc_) return mgi_fail(rc_, #call); } while (0)
 int    mgi_upload(mg_solver *s, const double *h, size_t n, double **d);   /* a new device array holding n host doubles */
 double mgi_wall(void);
 int    mgi_start(mg_solver *s);                          /* src/solver.c:1512-1523: ||b||, u0 = 0, rnorm[0], every level flag reset, iter = 0 */

@@ -18,12 +18,11 @@
  * (mg_solver_internal.h).  With mg_config.xline_chunk the x sweeps of a level that has separators are mg_xline_chunk.c's.
  */
 #include "mg_solver_internal.h"
+#include "mg_line_factor.h"
 #include <stdlib.h>
 #include <string.h>
 
-#define CHK(call) do { int rc_ = (call); if (rc_) return mgi_fail(rc_, #call); } while (0)
-
-long mg_xline_stride(int n, int uniform) { return uniform ? 0 : ((long)n + 15) / 16 * 16; }
+long mg_xline_stride(int n, int uniform) { return uniform ? 0 : (long)round16((size_t)n); }
 
 /* g of `rows` grid rows (1 on the uniform mesh: ctab's first row), n columns each, at a stride of gs doubles (0 allowed when rows == 1) */
 void mg_xline_factor(int n, int rows, const double *ctab, long gs, double *g) {

@@ -10,7 +10,7 @@
  *             q = E g_j are one rounded product each, formed by the kernels and by chunk_solve below)
  *   v, w      the spikes T_k^-1 (W e_a) and T_k^-1 (E e_{b-1}) of chunk k = [a, b), by the two substitutions of the sweep on that right-hand
  *             side; v = 0 on chunk 0, w = 0 on chunk K, both 0 in the separator columns (stored zeros: the edge cases are exact)
- *   SL SG SQ  band_factor's recurrence (mg_line_chunk.c) on the Schur rows d_q = (C - W w[s-1]) - E v[s+1], sub_q = -(W v[s-1]),
+ *   SL SG SQ  band_factor's recurrence (mg_line_factor.h) on the Schur rows d_q = (C - W w[s-1]) - E v[s+1], sub_q = -(W v[s-1]),
  *             sup_q = -(E w[s+1]) (s = n - 1: d_q = C - W w[s-1], sup_q = 0), per grid row; stored separator-major, entry [q sstride + i],
  *             so that a lane that owns a row reads them coalesced (sstride = 0 on the uniform mesh: one double per separator, entry [q])
  *
@@ -21,26 +21,8 @@
  * file is the only host code that calls the four kernels; mg_solver.c and mg_xline.c refer to it weakly (mg_solver_internal.h).
  */
 #include "mg_solver_internal.h"
+#include "mg_line_factor.h"
 #include <stdlib.h>
-
-#define CHK(call) do { int rc_ = (call); if (rc_) return mgi_fail(rc_, #call); } while (0)
-
-static size_t round16(size_t n) { return (n + 15) / 16 * 16; }
-
-/* band_factor of mg_line_chunk.c: line_factor's recurrence on three bands of n entries */
-static void band_factor(int n, const double *sub, const double *dia, const double *sup, double *lt, double *gt, double *qt) {
-    if (n < 1) return;
-    double m = dia[0];
-    gt[0] = 1.0 / m;
-    lt[0] = 0.0;
-    for (int i = 1; i < n; i++) {
-        lt[i] = sub[i] * gt[i - 1];
-        const double t = lt[i] * sup[i - 1];
-        m = dia[i] - t;
-        gt[i] = 1.0 / m;
-    }
-    for (int i = 0; i < n; i++) qt[i] = sup[i] * gt[i];
-}
 
 /* the two substitutions of the sweep on the columns [a, b) of x, in place: r -> x' */
 static void chunk_solve(double W, double E, const double *g, int a, int b, double *x) {
@@ -118,7 +100,7 @@ int mg_xline_chunk_tables(mg_solver *s, int lev, const double *ctab) {
                 sup[q] = -t;
             }
         }
-        band_factor(K, sub, dia, sup, fl, fg, fq);
+        band_factor(K, 1, sub, dia, sup, fl, fg, fq);
         for (int q = 0; q < K; q++) {
             const size_t at = ss ? (size_t)q * (size_t)ss + (size_t)i : (size_t)q;
             SLt[at] = fl[q]; SGt[at] = fg[q]; SQt[at] = fq[q];

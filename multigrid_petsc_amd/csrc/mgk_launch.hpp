@@ -1,18 +1,26 @@
 // mgk_launch.hpp -- the launch rules of libmgk.so's host side, each stated once (included by mgk_dev.hpp, after mgk_ctx and the tuning knobs):
-// wave width -> kernel instantiation, the cut of the marching axis into chunks, the far-plane fields of the slab launches, the stencil
+// wave width and ring depth -> kernel instantiation, the cut of the marching axis into chunks, the far-plane fields of the slab launches, the stencil
 // coefficients of the argument structs.  Host code only: nothing in here changes what a kernel computes.
 #pragma once
 #include <type_traits>
 #include "mgk_pow2.h"
 
-// ---- wave width: the runtime number of waves per row `w` picks the compile-time WX among WXS (ascending): the first one with w <= WX, the
-// last one for anything wider.  f is called with std::integral_constant<int, WX>.  The instantiations are those of the listed widths only.
-template <int W0, int... WS, typename F>
-static inline void with_width(int w, F &&f) {
-    if constexpr (sizeof...(WS) == 0) f(std::integral_constant<int, W0>{});
-    else if (w <= W0) f(std::integral_constant<int, W0>{});
-    else with_width<WS...>(w, f);
+// ---- a run-time value picks one of a listed pack of compile-time integers: the first V of VS, in the order listed, that MATCH::ok(v, V)
+// accepts, the last one for anything else.  f is called with std::integral_constant<int, V>.  The instantiations are those of the listed
+// values only.
+template <typename MATCH, int V0, int... VS, typename F>
+static inline void with_listed(int v, F &&f) {
+    if constexpr (sizeof...(VS) == 0) f(std::integral_constant<int, V0>{});
+    else if (MATCH::ok(v, V0)) f(std::integral_constant<int, V0>{});
+    else with_listed<MATCH, VS...>(v, f);
 }
+struct FitsIn { static bool ok(int v, int V) { return v <= V; } };
+struct Equals { static bool ok(int v, int V) { return v == V; } };
+// wave width: the runtime number of waves per row `w` picks the compile-time WX among WXS (ascending): the first one with w <= WX, the
+// last one for anything wider
+template <int... WXS, typename F> static inline void with_width(int w, F &&f) { with_listed<FitsIn, WXS...>(w, f); }
+// ring depth of the line marches: the knob's value `d` (line_depth(), xline_depth()) picks the built D equal to it, the last one listed otherwise
+template <int... DS, typename F> static inline void with_depth(int d, F &&f) { with_listed<Equals, DS...>(d, f); }
 template <typename F> static inline void width_1248(int w, F &&f) { with_width<1, 2, 4, 8>(w, f); }
 template <typename F> static inline void width_48(int w, F &&f) { with_width<4, 8>(w, f); }      // the pj2 kernels: rows of 512 / 1024 only
 // LAUNCH_WX(width_1248, w, (k_foo<T, WX, 3>), nblk, stream, args...): blocks of 64 * WX threads; `kernel` names WX
@@ -20,6 +28,13 @@ template <typename F> static inline void width_48(int w, F &&f) { with_width<4, 
     pick(w, [&](auto wx_) {                                                                           \
         constexpr int WX = decltype(wx_)::value;                                                      \
         hipLaunchKernelGGL(kernel, dim3((unsigned)(nblk)), dim3(64 * WX), 0, s, __VA_ARGS__);         \
+    })
+// LAUNCH_DEPTH_ZERO(line_depths, d, zero, k_foo, grid, stream, args...): one wave per block; `kernel` is a template on <D, ZERO>
+#define LAUNCH_DEPTH_ZERO(pick, d, zero, kernel, grid, s, ...)                                        \
+    pick(d, [&](auto d_) {                                                                            \
+        constexpr int D = decltype(d_)::value;                                                        \
+        if (zero) hipLaunchKernelGGL((kernel<D, true>), grid, dim3(64), 0, s, __VA_ARGS__);           \
+        else hipLaunchKernelGGL((kernel<D, false>), grid, dim3(64), 0, s, __VA_ARGS__);               \
     })
 
 // ---- chunks of the marching axis.  `extent` planes (rows) are cut into `nch` chunks -- by default as many as bring `tiles` tiles to

@@ -18,8 +18,7 @@
 // Stores: every pass reads what the one before it wrote, so fields within the 256 MB Infinity Cache are stored
 // normally and only larger ones non-temporally (mgk_store_nt_2d); mgk_set_tuning(variant = 0 / 1) forces one policy, and its second
 // argument (> 0) the prefetch depth (rounded down to a built one: 8, 16, 32).
-#include "mgk_dev.hpp"
-#include <type_traits>
+#include "mgk_line_dev.hpp"
 
 namespace {
 
@@ -34,22 +33,8 @@ struct LineArgs {
 };
 
 constexpr int LINE_U = 32;                      // rows per unrolled period: two table chunks of 16 rows, a multiple of every ring depth
-constexpr int LINE_RECORDS = 0x7ffffff0;        // every buffer window: far more than a window spans (the host checks the pitch) ...
-constexpr unsigned LINE_OOB = 0x7ffffff8u;      // ... and below the lane offset of a lane that must not store: the hardware drops its store
-constexpr long LINE_MAX_PITCH = 1L << 21;       // (LINE_U + 32 + 3) rows of a window stay below 2^31 bytes
+static_assert((LINE_U + 32 + 3) * LINE_MAX_PITCH * 8 < (1L << 31), "the rows of a window: a period, the deepest ring, the rows around them");
 
-typedef unsigned int line_u2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ bool line_nt(const LineArgs &a) { return a.nt < 0 ? mgk_store_nt_2d(a.ny, a.rs) : a.nt != 0; }
-// a window of a field: column cb and row `row` at offset 0.  Rows are addressed by a scalar byte offset, columns by one constant VGPR.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t line_window(const double *p, int cb, long row, long rs) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)((uintptr_t)p + (uintptr_t)((cb + row * rs) * 8)), 0, LINE_RECORDS, 0x00020000);
-}
-__device__ __forceinline__ double line_ld(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-}
-template <bool NT> __device__ __forceinline__ void line_st(double v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(line_u2, v), r, voff, soff, NT ? 2 : 0);
-}
 // lane K of every row of 16 lanes, to all lanes of that row (DPP row_newbcast): a table value that lane K of each row loaded
 template <int K> __device__ __forceinline__ double line_bcast(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
@@ -57,10 +42,6 @@ template <int K> __device__ __forceinline__ double line_bcast(double v) {
     hi = __builtin_amdgcn_mov_dpp(hi, 0x150 + K, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
 }
-template <int K, int N> struct LineUnroll {
-    template <class F> static __device__ __forceinline__ void run(F &&f) { f(std::integral_constant<int, K>{}); LineUnroll<K + 1, N>::run(f); }
-};
-template <int N> struct LineUnroll<N, N> { template <class F> static __device__ __forceinline__ void run(F &&) {} };
 
 // Both bodies: a period of LINE_U rows is ONE basic block.  Row i consumes ring slot i mod D and only then reloads it for row i + D; a
 // scheduling barrier after every row keeps that order, so the ring stays in its registers and the wait before a row leaves the loads and
@@ -196,16 +177,16 @@ __device__ __forceinline__ void line_backward_body(const LineArgs &a) {
 
 template <int D, bool ZERO>
 __global__ void __launch_bounds__(64) k_line_forward(const LineArgs a) {
-    if (line_nt(a)) line_forward_body<D, ZERO, true>(a); else line_forward_body<D, ZERO, false>(a);
+    if (line_store_nt(a.nt, a.ny, a.rs)) line_forward_body<D, ZERO, true>(a); else line_forward_body<D, ZERO, false>(a);
 }
 template <int D, bool ZERO>
 __global__ void __launch_bounds__(64) k_line_backward(const LineArgs a) {
-    if (line_nt(a)) line_backward_body<D, ZERO, true>(a); else line_backward_body<D, ZERO, false>(a);
+    if (line_store_nt(a.nt, a.ny, a.rs)) line_backward_body<D, ZERO, true>(a); else line_backward_body<D, ZERO, false>(a);
 }
 
-bool line_geom_ok(const mgk_geom *g) { return g && g->dim == 2 && g->nz == 1 && g->nx >= 1 && g->ny >= 1 && g->pitch <= LINE_MAX_PITCH; }
 int line_depth() { return g_zchunk >= 32 ? 32 : g_zchunk >= 16 ? 16 : g_zchunk > 0 ? 8 : 16; }
-int line_policy() { return store_policy(); }
+// the built ring depths, as with_depth lists them: 8 and 32 by name, 16 for everything else
+template <typename F> void line_depths(int d, F &&f) { with_depth<8, 32, 16>(d, f); }
 
 }  // namespace
 
@@ -215,20 +196,6 @@ int mgk_preload_line() {
     return 0;
 }
 
-#define LINE_DISPATCH(KERNEL, zero, grid, s, a)                                                              \
-    do {                                                                                                     \
-        const int d_ = line_depth();                                                                         \
-        if (zero) {                                                                                          \
-            if (d_ == 8) hipLaunchKernelGGL((KERNEL<8, true>), grid, dim3(64), 0, s, a);                     \
-            else if (d_ == 32) hipLaunchKernelGGL((KERNEL<32, true>), grid, dim3(64), 0, s, a);              \
-            else hipLaunchKernelGGL((KERNEL<16, true>), grid, dim3(64), 0, s, a);                            \
-        } else {                                                                                             \
-            if (d_ == 8) hipLaunchKernelGGL((KERNEL<8, false>), grid, dim3(64), 0, s, a);                    \
-            else if (d_ == 32) hipLaunchKernelGGL((KERNEL<32, false>), grid, dim3(64), 0, s, a);             \
-            else hipLaunchKernelGGL((KERNEL<16, false>), grid, dim3(64), 0, s, a);                           \
-        }                                                                                                    \
-    } while (0)
-
 extern "C" int mgk_line_forward_f64(mgk_ctx *c, const mgk_geom *g, const double *atab, const double *ltab, const double *gtab,
                                     const double *b, const double *u, double *z, void *stream) {
     if (!c || !line_geom_ok(g) || !ltab || !gtab || !b || !z || (u && !atab) || z == b || z == u)
@@ -236,9 +203,9 @@ extern "C" int mgk_line_forward_f64(mgk_ctx *c, const mgk_geom *g, const double 
     LineArgs a; memset(&a, 0, sizeof(a));
     a.u = u ? u + g->org : nullptr; a.b = b + g->org; a.out = z + g->org;
     a.t0 = atab; a.t1 = ltab; a.t2 = gtab;
-    a.nx = g->nx; a.ny = g->ny; a.rs = g->pitch; a.nt = line_policy();
+    a.nx = g->nx; a.ny = g->ny; a.rs = g->pitch; a.nt = store_policy();
     const dim3 grid((unsigned)((g->nx + 61) / 62));
-    LINE_DISPATCH(k_line_forward, u == nullptr, grid, S(c, stream), a);
+    LAUNCH_DEPTH_ZERO(line_depths, line_depth(), u == nullptr, k_line_forward, grid, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -250,9 +217,9 @@ extern "C" int mgk_line_backward_f64(mgk_ctx *c, const mgk_geom *g, const double
     LineArgs a; memset(&a, 0, sizeof(a));
     a.z = z + g->org; a.u = u ? u + g->org : nullptr; a.out = unew + g->org;
     a.t0 = qtab;
-    a.nx = g->nx; a.ny = g->ny; a.rs = g->pitch; a.scale = scale; a.nt = line_policy();
+    a.nx = g->nx; a.ny = g->ny; a.rs = g->pitch; a.scale = scale; a.nt = store_policy();
     const dim3 grid((unsigned)((g->nx + 63) / 64));
-    LINE_DISPATCH(k_line_backward, u == nullptr, grid, S(c, stream), a);
+    LAUNCH_DEPTH_ZERO(line_depths, line_depth(), u == nullptr, k_line_backward, grid, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
 }

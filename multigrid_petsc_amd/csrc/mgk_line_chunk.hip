@@ -13,7 +13,7 @@
 // row arithmetic is scalar, and the per-row tables are read through the constant address space at wave-uniform addresses: scalar loads
 // (DESIGN.md section 4 (xviii)).  The marches issue the loads of CH_R rows before they use the first.  Nothing outside the interior of an
 // output is written; loads touch the ghost ring at most.  Stores: mgk_store_nt_2d, or the policy mgk_set_tuning(0 / 1) forces.
-#include "mgk_dev.hpp"
+#include "mgk_line_dev.hpp"
 
 namespace {
 
@@ -32,7 +32,6 @@ constexpr int CH_R = 8;             // rows (reduce: separators, CH_S) whose loa
 constexpr int CH_S = 4;
 constexpr int CH_ROWS = 16;         // rows of a wave of the correction pass
 
-__device__ __forceinline__ bool chunk_nt(const ChunkArgs &a) { return a.nt < 0 ? mgk_store_nt_2d(a.ny, a.rs) : a.nt != 0; }
 template <bool NT> __device__ __forceinline__ void chunk_st(double *p, double v) {
     if (NT) __builtin_nontemporal_store(v, p); else *p = v;
 }
@@ -263,22 +262,22 @@ __device__ __forceinline__ void chunk_correct_body(const ChunkArgs &a, int piece
 
 template <bool ZERO>
 __global__ void __launch_bounds__(64) k_line_chunk_forward(const ChunkArgs a) {
-    if (chunk_nt(a)) chunk_forward_body<ZERO, true>(a); else chunk_forward_body<ZERO, false>(a);
+    if (line_store_nt(a.nt, a.ny, a.rs)) chunk_forward_body<ZERO, true>(a); else chunk_forward_body<ZERO, false>(a);
 }
 __global__ void __launch_bounds__(64) k_line_chunk_backward(const ChunkArgs a) {
-    if (chunk_nt(a)) chunk_backward_body<true>(a); else chunk_backward_body<false>(a);
+    if (line_store_nt(a.nt, a.ny, a.rs)) chunk_backward_body<true>(a); else chunk_backward_body<false>(a);
 }
 __global__ void __launch_bounds__(64) k_line_chunk_reduce(const ChunkArgs a) {
-    if (chunk_nt(a)) chunk_reduce_body<true>(a); else chunk_reduce_body<false>(a);
+    if (line_store_nt(a.nt, a.ny, a.rs)) chunk_reduce_body<true>(a); else chunk_reduce_body<false>(a);
 }
 template <bool ZERO>
 __global__ void __launch_bounds__(64) k_line_chunk_correct(const ChunkArgs a, const int pieces) {
-    if (chunk_nt(a)) chunk_correct_body<ZERO, true>(a, pieces); else chunk_correct_body<ZERO, false>(a, pieces);
+    if (line_store_nt(a.nt, a.ny, a.rs)) chunk_correct_body<ZERO, true>(a, pieces); else chunk_correct_body<ZERO, false>(a, pieces);
 }
 
 // 2-D, a period of at least two rows, and no more chunks than a grid has rows
 bool chunk_geom_ok(const mgk_geom *g, int c) {
-    return g && g->dim == 2 && g->nz == 1 && g->nx >= 1 && g->ny >= 1 && c >= 2 && g->ny / c + 1 <= 65535;
+    return line_dims_ok(g) && c >= 2 && g->ny / c + 1 <= 65535;
 }
 ChunkArgs chunk_args(const mgk_geom *g, int c) {
     ChunkArgs a; memset(&a, 0, sizeof(a));

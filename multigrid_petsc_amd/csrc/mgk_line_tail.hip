@@ -23,7 +23,7 @@
 // Ghost rings are zeroed once at the start and never written.  What the phases need of a level -- sizes, offsets, the x table's address --
 // sits in LDS too (LtMeta): a run-time index into the argument struct's arrays would send the whole struct to scratch.
 #include "mgk_tail_dev.hpp"
-#include <type_traits>
+#include "mgk_line_dev.hpp"
 
 namespace {
 
@@ -51,7 +51,6 @@ struct LtOps { double r[LB], x[LB]; };            // r: r (forward) / z (backwar
 // the operands of line `t`: MODE 0 a column (y sweep: tables l, g, q in LDS), MODE 1 a row with the x table's one row in LDS (uniform mesh),
 // MODE 2 a row with its own row of the x table in global memory.  Step s of the line sits at base + s * st
 template <int MODE> __device__ __forceinline__ int lt_base(int m, int t) { return MODE == 0 ? m + t + 1 : (t + 1) * m + 1; }
-template <int K> using lt_ic = std::integral_constant<int, K>;
 
 // The march over `count` steps p = 0 .. count - 1 (count >= 1) of one line, everything off the dependent chain read ahead of it into
 // statically indexed registers: the table values (loadG) in blocks of GB steps, one block ahead -- GB = 16 is one 128-byte line of the x table
@@ -66,13 +65,13 @@ __device__ __forceinline__ void lt_march(int count, FG &&loadG, FL &&loadL, FC &
     auto pair = [&](int p0, const double (&g)[GB], auto go) __attribute__((always_inline)) {
         constexpr int GO = decltype(go)::value;
         loadL(p0 + LB, B);
-        chain(p0, A, g, lt_ic<GO>{});
+        chain(p0, A, g, line_ic<GO>{});
         loadL(p0 + 2 * LB, A);
-        chain(p0 + LB, B, g, lt_ic<GO + LB>{});
+        chain(p0 + LB, B, g, line_ic<GO + LB>{});
     };
     auto run = [&](int p0, const double (&g)[GB]) __attribute__((always_inline)) {
-        pair(p0, g, lt_ic<0>{});
-        if constexpr (GB == 16) pair(p0 + 8, g, lt_ic<8>{});
+        pair(p0, g, line_ic<0>{});
+        if constexpr (GB == 16) pair(p0 + 8, g, line_ic<8>{});
     };
     for (int p0 = 0; p0 < count; p0 += 2 * GB) {
         loadG(p0 + GB, Gb);

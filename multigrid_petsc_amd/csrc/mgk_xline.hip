@@ -11,20 +11,15 @@
 // lane l of wave ty holds row 62 ty + l - 1, the y neighbours of u come by DPP wave shifts, lanes 1 .. 62 store (tiles overlap by two
 // rows).  Backward: a point reads only itself, 64 rows per wave.
 // Memory stays coalesced: a step moves a TILE of 64 rows x 16 columns, one whole 128-byte line per row (interior column 0 sits at MGK_XOFF,
-// which is line-aligned), four rows per load instruction: lane (rr, cc) = (lane / 16, lane % 16) of load k moves row 16 rr + k, column cc.
-// The tile is transposed through LDS with a row pitch of 17 doubles.  By the bank rule of the 8-byte LDS accesses -- ds_read_b64: two
-// groups of 32 lanes, bank pair (a / 8) mod 32; ds_write_b64: four groups of 16 contiguous lanes, bank pair (a / 8) mod 16 -- all four
-// accesses are conflict-free: row-wise write and read touch (272 rr + 17 k + cc), 16 consecutive doubles per group of 16 lanes and, as
-// 272 = 16 (mod 32), 32 consecutive ones per half wave; the transposed read and write touch (17 lane + c), distinct mod 32 in a half wave
-// and mod 16 in 16 contiguous lanes because 17 is odd.  z and u' go back the same way: lane-per-row values -> LDS -> line-wide stores.
+// which is line-aligned), transposed through LDS with a row pitch of 17 doubles, conflict-free in all four accesses: the tile, its lane
+// struct and the bank rule are stated in mgk_line_dev.hpp.  z and u' go back the same way: lane-per-row values -> LDS -> line-wide stores.
 // Tiles are loaded D steps ahead into a statically indexed register ring (the loop is unrolled by D tiles); loads and stores go through
 // buffer descriptors, a row or column that must not be touched has a lane offset out of range: such a load returns 0 and such a store is
 // dropped, so the ghost ring and the padding are neither read nor written.  The backward pass may write u in place (a tile is read whole
 // before it is written, and no other wave touches its rows): a sweep swaps no buffers.
 // Stores: as the y-line passes (mgk_store_nt_2d by size; mgk_set_tuning(variant = 0 / 1) forces one policy); the second knob (> 0) is the
 // ring depth in tiles (rounded down to a built one: 1, 2, 3; default 1).
-#include "mgk_dev.hpp"
-#include <type_traits>
+#include "mgk_line_dev.hpp"
 
 namespace {
 
@@ -38,58 +33,16 @@ struct XLineArgs {
     int nt;                         // store policy: < 0 by size, 0 ordinary, 1 non-temporal
 };
 
-constexpr int XT = 16;                          // columns per tile: one 128-byte line per row
-constexpr int XP = XT + 1;                      // LDS row pitch in doubles (odd: see the bank rule above)
-constexpr int XTILE = 64 * XP;                  // doubles of one tile in LDS
-constexpr int XL_RECORDS = 0x7ffffff0;          // every buffer window: far more than a window spans (the host checks the pitch) ...
-constexpr unsigned XL_OOB = 0x7ffffff8u;        // ... and below the lane offset of a lane that must not load or store
-constexpr long XL_MAX_PITCH = 1L << 21;         // 64 rows of a window and a row of 2^21 doubles stay below 2^31 bytes
-
-typedef unsigned int xl_u2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ bool xl_nt(const XLineArgs &a) { return a.nt < 0 ? mgk_store_nt_2d(a.ny, a.rs) : a.nt != 0; }
-// a window of a field or of the table: row `row`, column 0 at offset 0
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t xl_window(const double *p, long row, long rs) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)((uintptr_t)p + (uintptr_t)(row * rs * 8)), 0, XL_RECORDS, 0x00020000);
-}
-__device__ __forceinline__ double xl_ld(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-}
-template <bool NT> __device__ __forceinline__ void xl_st(double v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(xl_u2, v), r, voff, soff, NT ? 2 : 0);
-}
-template <int K, int N> struct XlUnroll {
-    template <class F> static __device__ __forceinline__ void run(F &&f) { f(std::integral_constant<int, K>{}); XlUnroll<K + 1, N>::run(f); }
-};
-template <int N> struct XlUnroll<N, N> { template <class F> static __device__ __forceinline__ void run(F &&) {} };
-
-// what both passes know about their lane: in the row-wise form of a tile lane (rr, cc) moves row r0 + 16 rr + k with load / store k
-struct XlLane {
-    int lane, rr, cc, rq;           // rq: the row of load 0
-    unsigned vf, vg;                // lane offsets (bytes) into a field window and into the table window
-    unsigned rs8, gs8;
-    int nx, ny;
-    __device__ __forceinline__ XlLane(const XLineArgs &a, int r0) {
-        lane = threadIdx.x; rr = lane >> 4; cc = lane & 15; rq = r0 + 16 * rr;
-        vf = (unsigned)((16 * rr * a.rs + cc) * 8); vg = (unsigned)((16 * rr * a.gs + cc) * 8);
-        rs8 = (unsigned)a.rs * 8u; gs8 = (unsigned)a.gs * 8u;
-        nx = a.nx; ny = a.ny;
-    }
-    __device__ __forceinline__ bool row_ok(int k) const { return (unsigned)(rq + k) < (unsigned)ny; }      // a grid row (not a ghost row)
-    __device__ __forceinline__ bool col_ok(int t) const { return t >= 0 && t * XT + cc < nx; }              // an interior column of tile t
-    __device__ __forceinline__ int rowwise(int k) const { return (16 * rr + k) * XP + cc; }                 // LDS index, row-wise form
-    __device__ __forceinline__ int transposed(int c) const { return lane * XP + c; }                        // LDS index, lane-per-row form
-};
-
 // Forward.  Ring slot s holds b and g of tile t and u of tile t + 1 (the residual of a tile's last column needs the next tile's first).
 template <int D, bool ZERO, bool NT>
 __device__ __forceinline__ void xline_forward_body(const XLineArgs &a, double *lds) {
     const int ty = __builtin_amdgcn_readfirstlane(blockIdx.x);
     const int r0 = ty * 62 - 1;                               // row of lane 0; -1 and ny are the ghost rows (zero, not read)
-    const XlLane L(a, r0);
+    const XLane L(a.rs, a.gs, a.nx, a.ny, r0);
     const int ntile = (a.nx + XT - 1) / XT;
     double *lu = lds, *lb = lds + XTILE, *lg = lds + 2 * XTILE, *lo = lds + 3 * XTILE;
-    const __amdgpu_buffer_rsrc_t wu = xl_window(a.u, r0, a.rs), wb = xl_window(a.b, r0, a.rs), wz = xl_window(a.out, r0, a.rs),
-                                 wg = xl_window(a.gt, r0, a.gs);
+    const __amdgpu_buffer_rsrc_t wu = line_window(a.u, r0, a.rs), wb = line_window(a.b, r0, a.rs), wz = line_window(a.out, r0, a.rs),
+                                 wg = line_window(a.gt, r0, a.gs);
     // the row constants of the lane's own row
     const long ri = min(max(r0 + L.lane, 0), a.ny - 1);
     double cS = 0.0, cC = 0.0, cE = 0.0, cN = 0.0;
@@ -97,32 +50,32 @@ __device__ __forceinline__ void xline_forward_body(const XLineArgs &a, double *l
     if (!ZERO) { cS = a.ct[5 * ri + 0]; cC = a.ct[5 * ri + 2]; cE = a.ct[5 * ri + 3]; cN = a.ct[5 * ri + 4]; }
     double qb[D][XT], qg[D][XT], qu[D][XT];
     auto issue = [&](int t, double (&rb)[XT], double (&rg)[XT], double (&ru)[XT]) {
-        const bool c0 = L.col_ok(t), c1 = L.col_ok(t + 1);
+        const bool c0 = L.col_ok_nonneg(t), c1 = L.col_ok_nonneg(t + 1);
         const unsigned so = (unsigned)max(t, 0) * (XT * 8u);
 #pragma unroll
         for (int k = 0; k < XT; k++) {
             const bool ok = L.row_ok(k);
-            rb[k] = xl_ld(wb, ok && c0 ? L.vf : XL_OOB, so + (unsigned)k * L.rs8);
-            rg[k] = xl_ld(wg, ok && c0 ? L.vg : XL_OOB, so + (unsigned)k * L.gs8);
-            ru[k] = ZERO ? 0.0 : xl_ld(wu, ok && c1 ? L.vf : XL_OOB, so + XT * 8u + (unsigned)k * L.rs8);
+            rb[k] = line_ld(wb, ok && c0 ? L.vf : LINE_OOB, so + (unsigned)k * L.rs8);
+            rg[k] = line_ld(wg, ok && c0 ? L.vg : LINE_OOB, so + (unsigned)k * L.gs8);
+            ru[k] = ZERO ? 0.0 : line_ld(wu, ok && c1 ? L.vf : LINE_OOB, so + XT * 8u + (unsigned)k * L.rs8);
         }
     };
     double uc[XT];                                            // u of the own row, the tile in hand
 #pragma unroll
     for (int c = 0; c < XT; c++) uc[c] = 0.0;
     if (!ZERO) {
-        const bool c0 = L.col_ok(0);
+        const bool c0 = L.col_ok_nonneg(0);
 #pragma unroll
-        for (int k = 0; k < XT; k++) lu[L.rowwise(k)] = xl_ld(wu, L.row_ok(k) && c0 ? L.vf : XL_OOB, (unsigned)k * L.rs8);
+        for (int k = 0; k < XT; k++) lu[L.rowwise(k)] = line_ld(wu, L.row_ok(k) && c0 ? L.vf : LINE_OOB, (unsigned)k * L.rs8);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int c = 0; c < XT; c++) uc[c] = lu[L.transposed(c)];
         __builtin_amdgcn_wave_barrier();
     }
-    XlUnroll<0, D>::run([&](auto sc) { constexpr int s = decltype(sc)::value; issue(s, qb[s], qg[s], qu[s]); });
+    LineUnroll<0, D>::run([&](auto sc) { constexpr int s = decltype(sc)::value; issue(s, qb[s], qg[s], qu[s]); });
     double uw = 0.0, y = 0.0, gp = 0.0;
     for (int t0 = 0; t0 < ntile; t0 += D) {
-        XlUnroll<0, D>::run([&](auto sc) {
+        LineUnroll<0, D>::run([&](auto sc) {
             constexpr int s = decltype(sc)::value;
             const int t = t0 + s;                             // t >= ntile: computes on zeros, stores nothing
 #pragma unroll
@@ -166,12 +119,12 @@ __device__ __forceinline__ void xline_forward_body(const XLineArgs &a, double *l
                 for (int c = 0; c < XT; c++) uc[c] = un[c];
             }
             __builtin_amdgcn_wave_barrier();
-            const bool c0 = L.col_ok(t);
+            const bool c0 = L.col_ok_nonneg(t);
             const unsigned so = (unsigned)t * (XT * 8u);
 #pragma unroll
             for (int k = 0; k < XT; k++) {
                 const bool edge = (k == 0 && L.rr == 0) || (k == XT - 1 && L.rr == 3);      // tile rows 0 and 63 only supply neighbours
-                xl_st<NT>(lo[L.rowwise(k)], wz, L.row_ok(k) && c0 && !edge ? L.vf : XL_OOB, so + (unsigned)k * L.rs8);
+                line_st<NT>(lo[L.rowwise(k)], wz, L.row_ok(k) && c0 && !edge ? L.vf : LINE_OOB, so + (unsigned)k * L.rs8);
             }
             __builtin_amdgcn_wave_barrier();
         });
@@ -183,31 +136,31 @@ template <int D, bool ZERO, bool NT>
 __device__ __forceinline__ void xline_backward_body(const XLineArgs &a, double *lds) {
     const int ty = __builtin_amdgcn_readfirstlane(blockIdx.x);
     const int r0 = ty * 64;
-    const XlLane L(a, r0);
+    const XLane L(a.rs, a.gs, a.nx, a.ny, r0);
     const int ntile = (a.nx + XT - 1) / XT;
     double *lz = lds, *lu = lds + XTILE, *lg = lds + 2 * XTILE, *lo = lds + 3 * XTILE;
-    const __amdgpu_buffer_rsrc_t wz = xl_window(a.z, r0, a.rs), wu = xl_window(a.u, r0, a.rs), wo = xl_window(a.out, r0, a.rs),
-                                 wg = xl_window(a.gt, r0, a.gs);
+    const __amdgpu_buffer_rsrc_t wz = line_window(a.z, r0, a.rs), wu = line_window(a.u, r0, a.rs), wo = line_window(a.out, r0, a.rs),
+                                 wg = line_window(a.gt, r0, a.gs);
     const long ri = min(r0 + L.lane, a.ny - 1);
     const double cE = a.ct[5 * ri + 3];
     const double sc = a.scale;
     const int last = a.nx - 1;
     double qz[D][XT], qg[D][XT], qu[D][XT];
     auto issue = [&](int t, double (&rz)[XT], double (&rg)[XT], double (&ru)[XT]) {
-        const bool c0 = L.col_ok(t);
+        const bool c0 = L.col_ok_any(t);
         const unsigned so = (unsigned)max(t, 0) * (XT * 8u);
 #pragma unroll
         for (int k = 0; k < XT; k++) {
             const bool ok = L.row_ok(k) && c0;
-            rz[k] = xl_ld(wz, ok ? L.vf : XL_OOB, so + (unsigned)k * L.rs8);
-            rg[k] = xl_ld(wg, ok ? L.vg : XL_OOB, so + (unsigned)k * L.gs8);
-            ru[k] = ZERO ? 0.0 : xl_ld(wu, ok ? L.vf : XL_OOB, so + (unsigned)k * L.rs8);
+            rz[k] = line_ld(wz, ok ? L.vf : LINE_OOB, so + (unsigned)k * L.rs8);
+            rg[k] = line_ld(wg, ok ? L.vg : LINE_OOB, so + (unsigned)k * L.gs8);
+            ru[k] = ZERO ? 0.0 : line_ld(wu, ok ? L.vf : LINE_OOB, so + (unsigned)k * L.rs8);
         }
     };
-    XlUnroll<0, D>::run([&](auto sq) { constexpr int s = decltype(sq)::value; issue(ntile - 1 - s, qz[s], qg[s], qu[s]); });
+    LineUnroll<0, D>::run([&](auto sq) { constexpr int s = decltype(sq)::value; issue(ntile - 1 - s, qz[s], qg[s], qu[s]); });
     double e = 0.0;
     for (int t0 = 0; t0 < ntile; t0 += D) {
-        XlUnroll<0, D>::run([&](auto sq) {
+        LineUnroll<0, D>::run([&](auto sq) {
             constexpr int s = decltype(sq)::value;
             const int t = ntile - 1 - (t0 + s);               // t < 0: computes on zeros, stores nothing
 #pragma unroll
@@ -235,10 +188,10 @@ __device__ __forceinline__ void xline_backward_body(const XLineArgs &a, double *
                 lo[L.transposed(c)] = ZERO ? se : ut[c] + se;
             }
             __builtin_amdgcn_wave_barrier();
-            const bool c0 = L.col_ok(t);
+            const bool c0 = L.col_ok_any(t);
             const unsigned so = (unsigned)max(t, 0) * (XT * 8u);
 #pragma unroll
-            for (int k = 0; k < XT; k++) xl_st<NT>(lo[L.rowwise(k)], wo, L.row_ok(k) && c0 ? L.vf : XL_OOB, so + (unsigned)k * L.rs8);
+            for (int k = 0; k < XT; k++) line_st<NT>(lo[L.rowwise(k)], wo, L.row_ok(k) && c0 ? L.vf : LINE_OOB, so + (unsigned)k * L.rs8);
             __builtin_amdgcn_wave_barrier();
         });
     }
@@ -247,18 +200,20 @@ __device__ __forceinline__ void xline_backward_body(const XLineArgs &a, double *
 template <int D, bool ZERO>
 __global__ void __launch_bounds__(64) k_xline_forward(const XLineArgs a) {
     __shared__ double lds[4 * XTILE];
-    if (xl_nt(a)) xline_forward_body<D, ZERO, true>(a, lds); else xline_forward_body<D, ZERO, false>(a, lds);
+    if (line_store_nt(a.nt, a.ny, a.rs)) xline_forward_body<D, ZERO, true>(a, lds); else xline_forward_body<D, ZERO, false>(a, lds);
 }
 template <int D, bool ZERO>
 __global__ void __launch_bounds__(64) k_xline_backward(const XLineArgs a) {
     __shared__ double lds[4 * XTILE];
-    if (xl_nt(a)) xline_backward_body<D, ZERO, true>(a, lds); else xline_backward_body<D, ZERO, false>(a, lds);
+    if (line_store_nt(a.nt, a.ny, a.rs)) xline_backward_body<D, ZERO, true>(a, lds); else xline_backward_body<D, ZERO, false>(a, lds);
 }
 
 bool xline_geom_ok(const mgk_geom *g, long gstride) {
-    return g && g->dim == 2 && g->nz == 1 && g->nx >= 1 && g->ny >= 1 && g->pitch <= XL_MAX_PITCH && (gstride == 0 || (gstride >= g->nx && gstride <= XL_MAX_PITCH));
+    return line_geom_ok(g) && (gstride == 0 || (gstride >= g->nx && gstride <= LINE_MAX_PITCH));
 }
 int xline_depth() { return g_zchunk >= 3 ? 3 : g_zchunk == 2 ? 2 : 1; }    // 1: the fastest at every size measured (profiles/line/README.md)
+// the built ring depths, as with_depth lists them: 2 and 3 by name, 1 for everything else
+template <typename F> void xline_depths(int d, F &&f) { with_depth<2, 3, 1>(d, f); }
 
 }  // namespace
 
@@ -267,20 +222,6 @@ int mgk_preload_xline() {
     HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_xline_backward<1, false>)));
     return 0;
 }
-
-#define XLINE_DISPATCH(KERNEL, zero, grid, s, a)                                                             \
-    do {                                                                                                     \
-        const int d_ = xline_depth();                                                                        \
-        if (zero) {                                                                                          \
-            if (d_ == 2) hipLaunchKernelGGL((KERNEL<2, true>), grid, dim3(64), 0, s, a);                     \
-            else if (d_ == 3) hipLaunchKernelGGL((KERNEL<3, true>), grid, dim3(64), 0, s, a);                \
-            else hipLaunchKernelGGL((KERNEL<1, true>), grid, dim3(64), 0, s, a);                             \
-        } else {                                                                                             \
-            if (d_ == 2) hipLaunchKernelGGL((KERNEL<2, false>), grid, dim3(64), 0, s, a);                    \
-            else if (d_ == 3) hipLaunchKernelGGL((KERNEL<3, false>), grid, dim3(64), 0, s, a);               \
-            else hipLaunchKernelGGL((KERNEL<1, false>), grid, dim3(64), 0, s, a);                            \
-        }                                                                                                    \
-    } while (0)
 
 extern "C" int mgk_xline_forward_f64(mgk_ctx *c, const mgk_geom *g, const double *atab, const double *gtab, long gstride,
                                      const double *b, const double *u, double *z, void *stream) {
@@ -291,7 +232,7 @@ extern "C" int mgk_xline_forward_f64(mgk_ctx *c, const mgk_geom *g, const double
     a.ct = atab; a.gt = gtab; a.gs = gstride;
     a.nx = g->nx; a.ny = g->ny; a.rs = g->pitch; a.nt = store_policy();
     const dim3 grid((unsigned)((g->ny + 61) / 62));
-    XLINE_DISPATCH(k_xline_forward, u == nullptr, grid, S(c, stream), a);
+    LAUNCH_DEPTH_ZERO(xline_depths, xline_depth(), u == nullptr, k_xline_forward, grid, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -305,7 +246,7 @@ extern "C" int mgk_xline_backward_f64(mgk_ctx *c, const mgk_geom *g, const doubl
     a.ct = atab; a.gt = gtab; a.gs = gstride;
     a.nx = g->nx; a.ny = g->ny; a.rs = g->pitch; a.scale = scale; a.nt = store_policy();
     const dim3 grid((unsigned)((g->ny + 63) / 64));
-    XLINE_DISPATCH(k_xline_backward, u == nullptr, grid, S(c, stream), a);
+    LAUNCH_DEPTH_ZERO(xline_depths, xline_depth(), u == nullptr, k_xline_backward, grid, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
 }

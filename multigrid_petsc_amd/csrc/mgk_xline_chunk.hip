@@ -16,11 +16,11 @@
 //                                  stride-0 table are loaded once; x = (x' - xi_{k-1} v) - xi_k w, u' = u + s x
 // fp64, no FMA (-ffp-contract=off).  Every wave is a block of its own; the chunk comes from blockIdx through readfirstlane.  The two marches
 // move tiles of 64 rows x 16 columns, one 128-byte line per row, transposed through the wave's own LDS at a pitch of 17 doubles, through
-// buffer descriptors: mgk_xline.hip's scheme (the bank rule and the out-of-range lane offset are stated there) with a ring of one tile.  c is
+// buffer descriptors: mgk_xline.hip's scheme (the bank rule and the out-of-range lane offset are stated in mgk_line_dev.hpp) with a ring of one tile.  c is
 // a multiple of 16, so a chunk starts on a line, is a whole number of tiles, and its separator is the last column of its last tile.
 // Nothing outside the interior of an output is written; neither the ghost ring nor the padding of an input is read; an entry of sep the
 // definition never forms is neither written nor read.  Stores: mgk_store_nt_2d, or the policy mgk_set_tuning(0 / 1) forces.
-#include "mgk_dev.hpp"
+#include "mgk_line_dev.hpp"
 
 namespace {
 
@@ -37,45 +37,9 @@ struct XChunkArgs {
     int nt;                         // store policy: < 0 by size, 0 ordinary, 1 non-temporal
 };
 
-constexpr int XT = 16;                          // columns per tile: one 128-byte line per row
-constexpr int XP = XT + 1;                      // LDS row pitch in doubles (odd: the bank rule of mgk_xline.hip)
-constexpr int XTILE = 64 * XP;                  // doubles of one tile in LDS
-constexpr int XC_RECORDS = 0x7ffffff0;          // every buffer window: far more than a window spans (the host checks the pitch) ...
-constexpr unsigned XC_OOB = 0x7ffffff8u;        // ... and below the lane offset of a lane that must not load or store
-constexpr long XC_MAX_PITCH = 1L << 21;         // 64 rows of a window and a row of 2^21 doubles stay below 2^31 bytes
 constexpr int XC_S = 4;                         // reduce: separators whose loads are in flight together
 constexpr int XC_R = 8;                         // correct: rows whose loads are in flight together ...
 constexpr int XC_ROWS = 16;                     // ... and rows of a wave
-
-typedef unsigned int xc_u2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ bool xc_nt(const XChunkArgs &a) { return a.nt < 0 ? mgk_store_nt_2d(a.ny, a.rs) : a.nt != 0; }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t xc_window(const double *p, long row, long rs) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)((uintptr_t)p + (uintptr_t)(row * rs * 8)), 0, XC_RECORDS, 0x00020000);
-}
-__device__ __forceinline__ double xc_ld(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-}
-template <bool NT> __device__ __forceinline__ void xc_st(double v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(xc_u2, v), r, voff, soff, NT ? 2 : 0);
-}
-
-// what both marches know about their lane: in the row-wise form of a tile lane (rr, cc) moves row r0 + 16 rr + k with load / store k
-struct XcLane {
-    int lane, rr, cc, rq;           // rq: the row of load 0
-    unsigned vf, vg;                // lane offsets (bytes) into a field window and into the table window
-    unsigned rs8, gs8;
-    int nx, ny;
-    __device__ __forceinline__ XcLane(const XChunkArgs &a, int r0) {
-        lane = threadIdx.x; rr = lane >> 4; cc = lane & 15; rq = r0 + 16 * rr;
-        vf = (unsigned)((16 * rr * a.rs + cc) * 8); vg = (unsigned)((16 * rr * a.gs + cc) * 8);
-        rs8 = (unsigned)a.rs * 8u; gs8 = (unsigned)a.gs * 8u;
-        nx = a.nx; ny = a.ny;
-    }
-    __device__ __forceinline__ bool row_ok(int k) const { return (unsigned)(rq + k) < (unsigned)ny; }      // a grid row (not a ghost row)
-    __device__ __forceinline__ bool col_ok(int t) const { return t * XT + cc < nx; }                        // an interior column of tile t >= 0
-    __device__ __forceinline__ int rowwise(int k) const { return (16 * rr + k) * XP + cc; }                 // LDS index, row-wise form
-    __device__ __forceinline__ int transposed(int c) const { return lane * XP + c; }                        // LDS index, lane-per-row form
-};
 
 // Forward, chunk k: the tiles [tb, te), the separator (k < K) the last column of tile te - 1.  The ring slot holds b and g of tile t and u of
 // tile t + 1 (the residual of a tile's last column needs the next tile's first -- at the separator the next chunk's first column).
@@ -83,13 +47,13 @@ template <bool ZERO, bool NT>
 __device__ __forceinline__ void xchunk_forward_body(const XChunkArgs &a, double *lds) {
     const int ty = __builtin_amdgcn_readfirstlane(blockIdx.x), k = __builtin_amdgcn_readfirstlane(blockIdx.y);
     const int r0 = ty * 62 - 1;                               // row of lane 0; -1 and ny are the ghost rows (zero, not read)
-    const XcLane L(a, r0);
+    const XLane L(a.rs, a.gs, a.nx, a.ny, r0);
     const int ntile = (a.nx + XT - 1) / XT;
     const bool hassep = k < a.K;
     const int tb = k * (a.c / XT), te = hassep ? tb + a.c / XT : ntile;
     double *lu = lds, *lb = lds + XTILE, *lg = lds + 2 * XTILE, *lo = lds + 3 * XTILE;
-    const __amdgpu_buffer_rsrc_t wu = xc_window(a.u, r0, a.rs), wb = xc_window(a.b, r0, a.rs), wz = xc_window(a.t, r0, a.rs),
-                                 wg = xc_window(a.t0, r0, a.gs);
+    const __amdgpu_buffer_rsrc_t wu = line_window(a.u, r0, a.rs), wb = line_window(a.b, r0, a.rs), wz = line_window(a.t, r0, a.rs),
+                                 wg = line_window(a.t0, r0, a.gs);
     const int row = r0 + L.lane;
     const bool mine = L.lane >= 1 && L.lane <= 62 && row < a.ny;       // a row this lane stores
     const long ri = min(max(row, 0), a.ny - 1);
@@ -98,14 +62,14 @@ __device__ __forceinline__ void xchunk_forward_body(const XChunkArgs &a, double 
     if (!ZERO) { cS = a.ct[5 * ri + 0]; cC = a.ct[5 * ri + 2]; cE = a.ct[5 * ri + 3]; cN = a.ct[5 * ri + 4]; }
     double qb[XT], qg[XT], qu[XT];
     auto issue = [&](int t) {                                 // t >= te: nothing is loaded
-        const bool c0 = t < te && L.col_ok(t), c1 = t < te && L.col_ok(t + 1);
+        const bool c0 = t < te && L.col_ok_nonneg(t), c1 = t < te && L.col_ok_nonneg(t + 1);
         const unsigned so = (unsigned)t * (XT * 8u);
 #pragma unroll
         for (int q = 0; q < XT; q++) {
             const bool ok = L.row_ok(q);
-            qb[q] = xc_ld(wb, ok && c0 ? L.vf : XC_OOB, so + (unsigned)q * L.rs8);
-            qg[q] = xc_ld(wg, ok && c0 ? L.vg : XC_OOB, so + (unsigned)q * L.gs8);
-            qu[q] = ZERO ? 0.0 : xc_ld(wu, ok && c1 ? L.vf : XC_OOB, so + XT * 8u + (unsigned)q * L.rs8);
+            qb[q] = line_ld(wb, ok && c0 ? L.vf : LINE_OOB, so + (unsigned)q * L.rs8);
+            qg[q] = line_ld(wg, ok && c0 ? L.vg : LINE_OOB, so + (unsigned)q * L.gs8);
+            qu[q] = ZERO ? 0.0 : line_ld(wu, ok && c1 ? L.vf : LINE_OOB, so + XT * 8u + (unsigned)q * L.rs8);
         }
     };
     double uc[XT];                                            // u of the own row, the tile in hand
@@ -113,10 +77,10 @@ __device__ __forceinline__ void xchunk_forward_body(const XChunkArgs &a, double 
 #pragma unroll
     for (int c = 0; c < XT; c++) uc[c] = 0.0;
     if (!ZERO) {
-        const bool c0 = L.col_ok(tb);
+        const bool c0 = L.col_ok_nonneg(tb);
         const unsigned so = (unsigned)tb * (XT * 8u);
 #pragma unroll
-        for (int q = 0; q < XT; q++) lu[L.rowwise(q)] = xc_ld(wu, L.row_ok(q) && c0 ? L.vf : XC_OOB, so + (unsigned)q * L.rs8);
+        for (int q = 0; q < XT; q++) lu[L.rowwise(q)] = line_ld(wu, L.row_ok(q) && c0 ? L.vf : LINE_OOB, so + (unsigned)q * L.rs8);
         if (k > 0 && (unsigned)row < (unsigned)a.ny) uw = a.u[(long)row * a.rs + (long)tb * XT - 1];
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -173,12 +137,12 @@ __device__ __forceinline__ void xchunk_forward_body(const XChunkArgs &a, double 
             for (int c = 0; c < XT; c++) uc[c] = un[c];
         }
         __builtin_amdgcn_wave_barrier();
-        const bool c0 = L.col_ok(t);
+        const bool c0 = L.col_ok_nonneg(t);
         const unsigned so = (unsigned)t * (XT * 8u);
 #pragma unroll
         for (int q = 0; q < XT; q++) {
             const bool edge = (q == 0 && L.rr == 0) || (q == XT - 1 && L.rr == 3);      // tile rows 0 and 63 only supply neighbours
-            xc_st<NT>(lo[L.rowwise(q)], wz, L.row_ok(q) && c0 && !edge ? L.vf : XC_OOB, so + (unsigned)q * L.rs8);
+            line_st<NT>(lo[L.rowwise(q)], wz, L.row_ok(q) && c0 && !edge ? L.vf : LINE_OOB, so + (unsigned)q * L.rs8);
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -190,25 +154,25 @@ template <bool NT>
 __device__ __forceinline__ void xchunk_backward_body(const XChunkArgs &a, double *lds) {
     const int ty = __builtin_amdgcn_readfirstlane(blockIdx.x), k = __builtin_amdgcn_readfirstlane(blockIdx.y);
     const int r0 = ty * 64;
-    const XcLane L(a, r0);
+    const XLane L(a.rs, a.gs, a.nx, a.ny, r0);
     const int ntile = (a.nx + XT - 1) / XT;
     const bool hassep = k < a.K;
     const int tb = k * (a.c / XT), te = hassep ? tb + a.c / XT : ntile;
     const int cb = hassep ? k * a.c + a.c - 1 : a.nx;         // one past the chunk's last column
     double *lz = lds, *lg = lds + XTILE, *lo = lds + 2 * XTILE;
-    const __amdgpu_buffer_rsrc_t wz = xc_window(a.t, r0, a.rs), wg = xc_window(a.t0, r0, a.gs);
+    const __amdgpu_buffer_rsrc_t wz = line_window(a.t, r0, a.rs), wg = line_window(a.t0, r0, a.gs);
     const int row = r0 + L.lane;
     const long ri = min(row, a.ny - 1);
     const double cE = a.ct[5 * ri + 3];
     double qz[XT], qg[XT];
     auto issue = [&](int t) {                                 // t < tb: nothing is loaded
-        const bool c0 = t >= tb && L.col_ok(t);
+        const bool c0 = t >= tb && L.col_ok_nonneg(t);
         const unsigned so = (unsigned)max(t, 0) * (XT * 8u);
 #pragma unroll
         for (int q = 0; q < XT; q++) {
             const bool ok = L.row_ok(q) && c0;
-            qz[q] = xc_ld(wz, ok ? L.vf : XC_OOB, so + (unsigned)q * L.rs8);
-            qg[q] = xc_ld(wg, ok ? L.vg : XC_OOB, so + (unsigned)q * L.gs8);
+            qz[q] = line_ld(wz, ok ? L.vf : LINE_OOB, so + (unsigned)q * L.rs8);
+            qg[q] = line_ld(wg, ok ? L.vg : LINE_OOB, so + (unsigned)q * L.gs8);
         }
     };
     issue(te - 1);
@@ -238,10 +202,10 @@ __device__ __forceinline__ void xchunk_backward_body(const XChunkArgs &a, double
             lo[L.transposed(c)] = e;
         }
         __builtin_amdgcn_wave_barrier();
-        const bool c0 = L.col_ok(t) && !(septile && L.cc == XT - 1);   // the separator column stays
+        const bool c0 = L.col_ok_nonneg(t) && !(septile && L.cc == XT - 1);   // the separator column stays
         const unsigned so = (unsigned)t * (XT * 8u);
 #pragma unroll
-        for (int q = 0; q < XT; q++) xc_st<NT>(lo[L.rowwise(q)], wz, L.row_ok(q) && c0 ? L.vf : XC_OOB, so + (unsigned)q * L.rs8);
+        for (int q = 0; q < XT; q++) line_st<NT>(lo[L.rowwise(q)], wz, L.row_ok(q) && c0 ? L.vf : LINE_OOB, so + (unsigned)q * L.rs8);
         __builtin_amdgcn_wave_barrier();
     }
     if (row < a.ny) {
@@ -395,26 +359,25 @@ __device__ __forceinline__ void xchunk_correct_body(const XChunkArgs &a, int pie
 template <bool ZERO>
 __global__ void __launch_bounds__(64) k_xline_chunk_forward(const XChunkArgs a) {
     __shared__ double lds[4 * XTILE];
-    if (xc_nt(a)) xchunk_forward_body<ZERO, true>(a, lds); else xchunk_forward_body<ZERO, false>(a, lds);
+    if (line_store_nt(a.nt, a.ny, a.rs)) xchunk_forward_body<ZERO, true>(a, lds); else xchunk_forward_body<ZERO, false>(a, lds);
 }
 __global__ void __launch_bounds__(64) k_xline_chunk_backward(const XChunkArgs a) {
     __shared__ double lds[3 * XTILE];
-    if (xc_nt(a)) xchunk_backward_body<true>(a, lds); else xchunk_backward_body<false>(a, lds);
+    if (line_store_nt(a.nt, a.ny, a.rs)) xchunk_backward_body<true>(a, lds); else xchunk_backward_body<false>(a, lds);
 }
 __global__ void __launch_bounds__(64) k_xline_chunk_reduce(const XChunkArgs a) { xchunk_reduce_body(a); }
 template <bool ZERO>
 __global__ void __launch_bounds__(64) k_xline_chunk_correct(const XChunkArgs a, const int pieces) {
-    if (xc_nt(a)) xchunk_correct_body<ZERO, true>(a, pieces); else xchunk_correct_body<ZERO, false>(a, pieces);
+    if (line_store_nt(a.nt, a.ny, a.rs)) xchunk_correct_body<ZERO, true>(a, pieces); else xchunk_correct_body<ZERO, false>(a, pieces);
 }
 
 // 2-D, a period that is a positive multiple of the tile, no more chunks than a grid has rows, strides a window can address
 bool xchunk_geom_ok(const mgk_geom *g, int c, long stride) {
-    return g && g->dim == 2 && g->nz == 1 && g->nx >= 1 && g->ny >= 1 && c > 0 && c % XT == 0 && g->nx / c + 1 <= 65535 &&
-           g->pitch <= XC_MAX_PITCH && stride >= 0 && stride <= XC_MAX_PITCH;
+    return line_geom_ok(g) && c > 0 && c % XT == 0 && g->nx / c + 1 <= 65535 && stride >= 0 && stride <= LINE_MAX_PITCH;
 }
 XChunkArgs xchunk_args(const mgk_geom *g, int c) {
     XChunkArgs a; memset(&a, 0, sizeof(a));
-    a.nx = g->nx; a.ny = g->ny; a.c = c; a.K = g->nx / c; a.rs = g->pitch; a.ss = ((long)g->ny + 15) / 16 * 16; a.nt = store_policy();
+    a.nx = g->nx; a.ny = g->ny; a.c = c; a.K = g->nx / c; a.rs = g->pitch; a.ss = round16((long)g->ny); a.nt = store_policy();
     return a;
 }
 // the chunks a march is launched for: the last one only if it is not empty
