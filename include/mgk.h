@@ -682,7 +682,7 @@ enum mgk_tune {
     MGK_TUNE_SRR_TY4           = 41,   /* sweep_residual_restrict (whole grid): tiles of 4 rows, swept planes in LDS (k_srr4b) */
     MGK_TUNE_J2_ZERO_RINGB     = 45,   /* jacobi2 from the zero guess, fp64: k_jacobi2b, which fp64 leaves to fp32 by default */
     MGK_TUNE_PJ2_COPY          = 46,   /* prolong_jacobi2 (whole grid): the copying form k_pj2r instead of the unrolled k_pj2r3 */
-    MGK_TUNE_J3_2D_MARCH       = 50,   /* jacobi3_2d (mgk_kernels3.hip): the marching form on every size */
+    MGK_TUNE_J3_2D_MARCH       = 50,   /* jacobi3_2d (mgk_sweep3.hip): the marching form on every size */
     MGK_TUNE_J3_2D_CHUNK4      = 51,   /* jacobi3_2d: the short-chunk form, 4 rows */
     MGK_TUNE_J3_2D_CHUNK8      = 52,   /* jacobi3_2d: the short-chunk form, 8 rows */
     MGK_TUNE_DISPATCH_ORDER    = 53,   /* jacobi3_2d, jacobi3_3d: wave tiles in dispatch order */

@@ -1,6 +1,6 @@
-// mgk_dev.hpp -- what the translation units of libmgk.so share: context, error reporting, device helpers (16-byte lane vectors,
-// streaming accesses, wavefront reductions and DPP lane shifts, buffer-descriptor accesses).  Moved out of mgk_kernels.hip in round 3
-// so that new kernels live in a file of their own (mgk_kernels3.hip) and compile in seconds.
+// mgk_dev.hpp -- what the translation units of libmgk.so share: context, error reporting, the preload registry, device helpers (16-byte
+// lane vectors, streaming accesses, wavefront reductions and DPP lane shifts, buffer-descriptor accesses).  Shared so that a kernel family can
+// live in a unit of its own (mgk_tail.hip, mgk_sweep3.hip, mgk_krylov.hip, the line units) and a change to it recompiles that unit alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -35,13 +35,22 @@ extern thread_local int g_variant, g_zchunk;
 // the store policy the Krylov and line passes read from the knob: 0 ordinary, 1 non-temporal, -1 by field size
 static inline int store_policy() { return g_variant == MGK_TUNE_STORE_PLAIN ? 0 : g_variant == MGK_TUNE_STORE_NT ? 1 : -1; }
 int finish_to_host(mgk_ctx *c, int nparts, int nslots, hipStream_t s, double *host_out);
-int mgk_preload_kernels3();      // forces the code object of mgk_kernels3.hip to load (mgk_ctx_create)
-int mgk_preload_krylov();        // ... and that of mgk_krylov.hip
-int mgk_preload_line();          // ... and that of mgk_line.hip
-int mgk_preload_xline();         // ... and that of mgk_xline.hip
-int mgk_preload_line_chunk();    // ... and that of mgk_line_chunk.hip
-int mgk_preload_xline_chunk();   // ... and that of mgk_xline_chunk.hip
-int mgk_preload_line_tail();     // ... and that of mgk_line_tail.hip
+// MGK_PRELOAD_UNIT(kernel): ONE such line at file scope in every .hip unit, naming one of the unit's kernels (an instance the unit forms
+// anyway).  HIP loads a unit's code object at the first use of one of its kernels (~2 ms each); that load once fell inside the reference
+// driver's first KSPSolve, and it must never fall inside a graph capture: mgk_ctx_create walks this registry and loads every unit.  The
+// storage (mgk_kernels.hip) is constant-initialised -- a fixed array and a count, zero before any constructor runs -- so the order in
+// which the units' constructors run does not matter; a unit beyond MGK_PRELOAD_MAX makes mgk_ctx_create fail, it is not dropped silently.
+#define MGK_INTERNAL __attribute__((visibility("hidden")))      // internal to libmgk.so: not part of its dynamic symbol table
+#define MGK_PRELOAD_MAX 32
+extern MGK_INTERNAL const void *g_preload_kernels[MGK_PRELOAD_MAX];
+extern MGK_INTERNAL int g_preload_count;
+struct mgk_preload_unit {
+    explicit mgk_preload_unit(const void *kernel) {
+        if (g_preload_count < MGK_PRELOAD_MAX) g_preload_kernels[g_preload_count] = kernel;
+        g_preload_count++;
+    }
+};
+#define MGK_PRELOAD_UNIT(...) static const mgk_preload_unit mgk_preload_this_unit(reinterpret_cast<const void *>(__VA_ARGS__));
 #include "mgk_launch.hpp"        // the launch rules of the host side (they read the context and the knobs above)
 #define MGK_RESULT_SLOTS 64      // >= MGK_KRYLOV_MAX + 1: the dots of an Arnoldi step and the norm that follows them
 

@@ -191,11 +191,7 @@ bool kry_geom_ok(const mgk_geom *g) {
 
 }  // namespace
 
-int mgk_preload_krylov() {
-    hipFuncAttributes fa;
-    HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_kry_finish)));
-    return 0;
-}
+MGK_PRELOAD_UNIT(k_kry_finish)
 
 extern "C" int mgk_multi_dot_f64(mgk_ctx *c, const mgk_geom *g, int k, const double *const *v, const double *w, double *out_dev,
                                  double *out_host, void *stream) {

@@ -190,11 +190,7 @@ template <typename F> void line_depths(int d, F &&f) { with_depth<8, 32, 16>(d, 
 
 }  // namespace
 
-int mgk_preload_line() {
-    hipFuncAttributes fa;
-    HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_line_backward<16, false>)));
-    return 0;
-}
+MGK_PRELOAD_UNIT(k_line_backward<16, false>)
 
 extern "C" int mgk_line_forward_f64(mgk_ctx *c, const mgk_geom *g, const double *atab, const double *ltab, const double *gtab,
                                     const double *b, const double *u, double *z, void *stream) {

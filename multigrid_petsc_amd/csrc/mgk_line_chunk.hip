@@ -287,11 +287,7 @@ ChunkArgs chunk_args(const mgk_geom *g, int c) {
 
 }  // namespace
 
-int mgk_preload_line_chunk() {
-    hipFuncAttributes fa;
-    HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_line_chunk_backward)));
-    return 0;
-}
+MGK_PRELOAD_UNIT(k_line_chunk_backward)
 
 extern "C" int mgk_line_chunk_forward_f64(mgk_ctx *ctx, const mgk_geom *g, int c, const double *atab, const double *ltab, const double *gtab,
                                           const double *b, const double *u, double *t, void *stream) {

@@ -1,5 +1,5 @@
 // mgk_line_tail.hip -- the LDS-resident coarse levels of a LINE cycle in one launch: mgk_tail_cycle_line_f64, the
-// contract of mgk_tail_cycle_f64 (mgk_kernels.hip, k_tail) with line sweeps as the smoother.  One workgroup of 1024 lanes keeps u, z and b of
+// contract of mgk_tail_cycle_f64 (mgk_tail.hip, k_tail) with line sweeps as the smoother.  One workgroup of 1024 lanes keeps u, z and b of
 // every tail level in LDS, ghost rings included, and walks the loop of src/solver.c:1533-1544 over them with a workgroup barrier between
 // dependent phases.  fp64, no FMA (-ffp-contract=off), no inline assembly; bit-identical to the launch-by-launch loop over mgk_line_* /
 // mgk_xline_* / the residual, restriction and prolongation kernels (the definitions: tests/line_reference.py, tests/xline_reference.py).
@@ -269,11 +269,7 @@ __global__ void __launch_bounds__(1024) k_tail_line(const LineTailArgs a) {
 
 }  // namespace
 
-int mgk_preload_line_tail() {
-    hipFuncAttributes fa;
-    HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_tail_line)));
-    return 0;
-}
+MGK_PRELOAD_UNIT(k_tail_line)
 
 extern "C" int mgk_tail_cycle_line_f64(mgk_ctx *c, const mgk_geom *g0, int nlev, const int *n, int pc, const double *const *ctab,
                                        const double *const *ltab, const double *const *gtab, const double *const *qtab,

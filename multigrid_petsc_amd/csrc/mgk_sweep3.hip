@@ -1,5 +1,5 @@
-// mgk_kernels3.hip -- round 3: three-sweep passes (2-D independent-wave forms; 3-D forms below).  Same build flags as mgk_kernels.hip
-// (-O3 -ffp-contract=off, gfx950 only); shares mgk_dev.hpp with it.
+// mgk_sweep3.hip -- three-sweep passes (2-D independent-wave forms; 3-D forms below).  Same build flags as every unit of libmgk.so
+// (-O3 -ffp-contract=off, gfx950 only); shares mgk_dev.hpp with them.
 #include "mgk_dev.hpp"
 #include <type_traits>
 
@@ -698,11 +698,7 @@ extern "C" int mgk_flags_wait(mgk_ctx *c, void *const *flags, int n, unsigned lo
     HIPCHK(hipGetLastError());
     return 0;
 }
-int mgk_preload_kernels3() {
-    hipFuncAttributes fa;
-    HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_flag_set)));
-    return 0;
-}
+MGK_PRELOAD_UNIT(k_flag_set)
 extern "C" int mgk_flag_set(mgk_ctx *c, void *flag, unsigned long long value, void *stream) { void *f[1] = {flag}; return mgk_flags_set(c, f, 1, value, stream); }
 extern "C" int mgk_flag_wait(mgk_ctx *c, const void *flag, unsigned long long value, double timeout_s, void *status_u32, void *stream) {
     void *f[1] = {const_cast<void *>(flag)};

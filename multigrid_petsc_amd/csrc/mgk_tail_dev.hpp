@@ -1,11 +1,11 @@
 // mgk_tail_dev.hpp -- what the kernels that keep the tail of the hierarchy in the LDS of ONE workgroup share (k_tail, k_tail_cheby, k_tail_fmg in
-// mgk_kernels.hip; k_tail_line in mgk_line_tail.hip): the index of a point in an (n+2)^DIM array, the deal of a level's points over the lanes,
+// mgk_tail.hip; k_tail_line in mgk_line_tail.hip): the index of a point in an (n+2)^DIM array, the deal of a level's points over the lanes,
 // and the two transfers.  One definition of their arithmetic: every tail kernel restricts and prolongs with the same operations in the same order.
 #pragma once
 #include "mgk_dev.hpp"
 
 #define MGK_TAIL_MAXLEV 8
-// mgk_debug_tail_stamps (mgk_kernels.hip): where the tail kernels this thread launches deposit their clock pairs; null in production
+// mgk_debug_tail_stamps (mgk_tail.hip): where the tail kernels this thread launches deposit their clock pairs; null in production
 extern thread_local long long *g_tail_stamps;
 
 template <typename T, int DIM>

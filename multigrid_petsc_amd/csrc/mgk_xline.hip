@@ -217,11 +217,7 @@ template <typename F> void xline_depths(int d, F &&f) { with_depth<2, 3, 1>(d, f
 
 }  // namespace
 
-int mgk_preload_xline() {
-    hipFuncAttributes fa;
-    HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_xline_backward<1, false>)));
-    return 0;
-}
+MGK_PRELOAD_UNIT(k_xline_backward<1, false>)
 
 extern "C" int mgk_xline_forward_f64(mgk_ctx *c, const mgk_geom *g, const double *atab, const double *gtab, long gstride,
                                      const double *b, const double *u, double *z, void *stream) {

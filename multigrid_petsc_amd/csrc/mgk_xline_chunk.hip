@@ -385,11 +385,7 @@ unsigned xchunk_count(const XChunkArgs &a) { return (unsigned)(a.K + (a.nx > a.K
 
 }  // namespace
 
-int mgk_preload_xline_chunk() {
-    hipFuncAttributes fa;
-    HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_xline_chunk_backward)));
-    return 0;
-}
+MGK_PRELOAD_UNIT(k_xline_chunk_backward)
 
 extern "C" int mgk_xline_chunk_forward_f64(mgk_ctx *ctx, const mgk_geom *g, int c, const double *atab, const double *gtab, long gstride,
                                            const double *b, const double *u, double *t, double *sep, void *stream) {

@@ -1,4 +1,4 @@
-"""Round 3: three Richardson+Jacobi sweeps in one pass (csrc/mgk_kernels3.hip) against the CPU oracle on the same seeded inputs -- fields
+"""Round 3: three Richardson+Jacobi sweeps in one pass (csrc/mgk_sweep3.hip) against the CPU oracle on the same seeded inputs -- fields
 bit for bit (np.array_equal), sums of squares to 1e-13.  2-D: mgk_jacobi3_2d_f64 / _sumsq / _zero, mgk_prolong_jacobi3_2d_f64, on
 constant stencils (oracle/mgo.c) and on row tables (the canonical term order restated in numpy, as for the other row-table kernels).
 Reference operations: KSPSolve with max_it = 3, src/solver.c:1531, :1536, :1542; MatMult(pro) + VecAXPY :1540-1541; VecNorm :1546."""

@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
-"""Compare the device code of two builds of one translation unit, symbol by symbol.  CPU only.
+"""Compare the device code of two builds, symbol by symbol.  CPU only.  Each side is one translation unit or several: the union of the
+files of a side is compared, so a unit that was cut into several (or several merged into one) compares against what it was.
 
-    hipcc <HIPFLAGS of csrc/Makefile> --cuda-device-only -S -o before.s mgk_kernels.hip      (at the parent)
-    hipcc <HIPFLAGS of csrc/Makefile> --cuda-device-only -S -o after.s  mgk_kernels.hip      (at the change)
-    python tools/compare_device_asm.py before.s after.s
+    hipcc <HIPFLAGS of csrc/Makefile> --cuda-device-only -S -o parent/<unit>.s <unit>.hip      (at the parent, per unit)
+    hipcc <HIPFLAGS of csrc/Makefile> --cuda-device-only -S -o change/<unit>.s <unit>.hip      (at the change, per unit)
+    python tools/compare_device_asm.py parent/mgk_line.s change/mgk_line.s
+    python tools/compare_device_asm.py --before parent/mgk_kernels.s --after change/mgk_kernels.s change/mgk_tail.s
 
-Prints one line per symbol that is in one file only, whose instructions differ, or whose kernel descriptor (.amdhsa_* directives: VGPR /
-SGPR / AGPR counts, LDS and scratch size, ...) differs; prints nothing and exits 0 when the device code is the same.  Functions are matched
-by name, so moving an instantiation point (which reorders the functions and renumbers their local labels) is no difference: the function
-number in .LBB<function>_<block> labels is dropped before comparing, comments are stripped."""
+Prints one line per symbol that is on one side only, whose instructions differ, or whose kernel descriptor (.amdhsa_* directives: VGPR /
+SGPR / AGPR counts, LDS and scratch size, ...) differs, and one line per symbol that occurs in MORE THAN ONE FILE of a side (a kernel
+instantiated in two units); prints nothing and exits 0 when the device code is the same and every symbol has one home.  Functions are
+matched by name, so moving an instantiation point (which reorders the functions and renumbers their local labels) is no difference: the
+function number in .LBB<function>_<block> labels is dropped before comparing, comments are stripped."""
+import argparse
 import re
 import sys
 
@@ -46,15 +50,40 @@ def parse(path):
     return funcs, descs
 
 
+def parse_side(paths):
+    """Union of the files of one side; returns (functions, descriptors, number of symbols found in more than one file)."""
+    funcs, descs, home, twice = {}, {}, {}, 0
+    for path in paths:
+        f, d = parse(path)
+        for what, new, all_ in (("function", f, funcs), ("kernel descriptor", d, descs)):
+            for sym in sorted(new):
+                if sym in all_:
+                    print(f"{what} in two files: {sym} ({home[what, sym]} and {path})")
+                    twice += 1
+                else:
+                    all_[sym] = new[sym]
+                    home[what, sym] = path
+    return funcs, descs, twice
+
+
 def main():
-    if len(sys.argv) != 3:
-        sys.exit(__doc__)
-    (fa, da), (fb, db) = parse(sys.argv[1]), parse(sys.argv[2])
-    bad = 0
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("pair", nargs="*", help="before.s after.s (one file a side)")
+    ap.add_argument("--before", nargs="+", default=[], metavar="FILE.s")
+    ap.add_argument("--after", nargs="+", default=[], metavar="FILE.s")
+    args = ap.parse_args()
+    if len(args.pair) == 2 and not args.before and not args.after:
+        before, after = [args.pair[0]], [args.pair[1]]
+    elif not args.pair and args.before and args.after:
+        before, after = args.before, args.after
+    else:
+        ap.error("give either two files, or --before FILES --after FILES")
+    (fa, da, ta), (fb, db, tb) = parse_side(before), parse_side(after)
+    bad = ta + tb
     for what, a, b in (("function", fa, fb), ("kernel descriptor", da, db)):
         for sym in sorted(set(a) | set(b)):
             if sym not in a or sym not in b:
-                print(f"{what} only in {sys.argv[2] if sym in b else sys.argv[1]}: {sym}")
+                print(f"{what} only {'after' if sym in b else 'before'}: {sym}")
             elif a[sym] != b[sym]:
                 at = next((i for i, (x, y) in enumerate(zip(a[sym], b[sym])) if x != y), min(len(a[sym]), len(b[sym])))
                 print(f"{what} differs: {sym} (line {at} of {len(a[sym])} / {len(b[sym])})")

@@ -4,7 +4,7 @@
 set -e
 B=/opt/rocm/lib/llvm/bin
 T=$(mktemp -d)
-for LIB in ${2:-$(dirname "$0")/../multigrid_petsc_amd/csrc/mgk_kernels*.o}; do
+for LIB in ${2:-$(dirname "$0")/../multigrid_petsc_amd/csrc/mgk_*.o}; do
 $B/llvm-objcopy --dump-section .hip_fatbin=$T/fat.bin "$LIB" 2>/dev/null
 $B/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$T/fat.bin --output=$T/k.co --unbundle
 $B/llvm-objdump -d --no-show-raw-insn $T/k.co > $T/k.s

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Register / scratch figures of the k_jacobi3_2d and k_tail* instances, read from hipcc's -Rpass-analysis=kernel-resource-usage remarks
-(no GPU needed):  hipcc ... -Rpass-analysis=kernel-resource-usage -c mgk_kernels3.hip 2> log;  tools/kernel_resources.py log [name-filter]"""
+(no GPU needed):  hipcc ... -Rpass-analysis=kernel-resource-usage -c mgk_sweep3.hip 2> log;  tools/kernel_resources.py log [name-filter]"""
 import re
 import sys
 

@@ -2,10 +2,10 @@
 # VGPR / SGPR / LDS / scratch of the gfx950 kernels in libmgk.so whose name matches $1 (regex on the mangled name)
 # usage: tools/kernel_resources.sh k_jacobi3 [library]
 set -e
-# (one fat binary per translation unit: the objects csrc/mgk_kernels*.o are read, or the file given as $2)
+# (one fat binary per translation unit: the objects csrc/mgk_*.o are read, or the file given as $2)
 B=/opt/rocm/lib/llvm/bin
 T=$(mktemp -d)
-for LIB in ${2:-$(dirname "$0")/../multigrid_petsc_amd/csrc/mgk_kernels*.o}; do
+for LIB in ${2:-$(dirname "$0")/../multigrid_petsc_amd/csrc/mgk_*.o}; do
 $B/llvm-objcopy --dump-section .hip_fatbin=$T/fat.bin "$LIB" 2>/dev/null
 $B/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$T/fat.bin --output=$T/k.co --unbundle
 $B/llvm-readelf --notes $T/k.co | python3 -c "
