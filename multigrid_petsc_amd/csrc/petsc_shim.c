@@ -28,8 +28,9 @@
 /* ------------------------------------------------------------------ */
 static mgk_ctx *G = NULL;
 static int g_notice_pc = 0;
-static long g_lzstat[14];    /* lazy temporaries: [0] residual+restriction fused, [1] prolongation fused into a sweep, [2..4] deferred values that were
-                              * computed after all (residual, prolongation, correction), [5] deferred values overwritten unread */
+static long g_lzstat[16];    /* lazy temporaries: [0] residual+restriction fused, [1] prolongation fused into a sweep, [2..4] deferred values that were
+                              * computed after all (residual, prolongation, correction), [5] deferred values overwritten unread; ...; [14] three-sweep
+                              * passes (mgk_jacobi3_2d_*, mgk_prolong_jacobi3_2d_f64), [15] two-sweep passes of KSPSolve (mgk_jacobi2_2d_f64) */
 
 static void tc_shutdown(void);       /* the tail recorder's logs (below) */
 static void die(const char *what) {
@@ -107,9 +108,10 @@ PetscErrorCode PetscFinalize(void) {
         printf("[mgpetsc] lazy temporaries: %ld residual+restriction passes, %ld prolongation sweeps fused; computed after all: %ld residuals, "
                "%ld prolongations, %ld corrections; %ld dropped unread; %ld zero-guess sweeps out of the restriction's pass; %ld norm passes that store r and make the next sweep, %ld of those sweeps adopted; "
                "%ld norm passes that left r deferred, %ld of those residuals followed the old iterate into the work vector; "
-               "%ld coarse sub-cycles run as ONE tail launch, %ld recordings replayed call by call, %ld times their unread intermediates were computed after all\n",
+               "%ld coarse sub-cycles run as ONE tail launch, %ld recordings replayed call by call, %ld times their unread intermediates were computed after all; "
+               "%ld three-sweep passes, %ld two-sweep passes of KSPSolve\n",
                g_lzstat[0], g_lzstat[1], g_lzstat[2], g_lzstat[3], g_lzstat[4], g_lzstat[5], g_lzstat[7], g_lzstat[6], g_lzstat[8], g_lzstat[9], g_lzstat[10],
-               g_lzstat[11], g_lzstat[12], g_lzstat[13]);
+               g_lzstat[11], g_lzstat[12], g_lzstat[13], g_lzstat[14], g_lzstat[15]);
     tc_shutdown();
     if (G) { mgk_ctx_destroy(G); G = NULL; }
     for (int q = 0; q < g_nopt; q++) { free(g_opt[q].key); free(g_opt[q].val); }
@@ -329,6 +331,12 @@ static void lz_register(Vec v, int kind, struct _p_Mat *A, Vec b, Vec x) {
  * deferred value is dead, otherwise it is computed first */
 static void lz_before_write(Vec v, int full) {
     if (v->lz == LZ_TAIL && tc_recording_has(v)) tc_settle(v);      /* a write from outside the pattern: the recording is executed first */
+    /* tc_input_changing may hand v's buffer to a finished log and continue v on a spare one: whatever else is defined in terms of v (not the
+     * log's own ghosts, which follow the buffer) is computed while v still has it -- a P v deferred by MatMult(pro) was formed from the spare */
+    for (int q = 0; q < g_nlz; ) {
+        Vec L = g_lz[q];
+        if (L != v && L->lz != LZ_TAIL && (L->lz_b == v || L->lz_x == v)) { lz_settle(L); q = 0; } else q++;
+    }
     tc_input_changing(v, full);
     for (int q = 0; q < g_nlz; ) {
         Vec L = g_lz[q];
@@ -1096,7 +1104,14 @@ static void lz_settle(Vec v) {
     struct _p_Mat *A = v->lz_A; Vec b = v->lz_b, x = v->lz_x;
     struct _p_Mat *A2 = v->lz_A2;
     if (!kind) return;
-    if (kind == LZ_TAIL) { tc_settle(v); return; }
+    if (kind == LZ_TAIL) {
+        /* a recording that is replayed call by call goes through the ordinary paths, which defer in their turn: the restricted right-hand
+         * side it had taken comes back as LZ_RR.  The caller wants the value, so that is computed too (a Chebyshev KSPSolve on it -- which
+         * the recorder is not asked about -- read the buffer before the restriction had run) */
+        tc_settle(v);
+        if (v->lz && v->lz != LZ_TAIL) lz_settle(v);
+        return;
+    }
     lz_drop(v);
     if (kind == LZ_RR) { rr_now(A, A2, b, x, v, NULL, 1.0, 1.0, NULL); return; }
     g_lzstat[1 + kind]++;
@@ -2103,14 +2118,14 @@ PetscErrorCode KSPSolve(KSP k, Vec b, Vec x) {
                     if (rrA || !k->guess_nonzero) DEV(mgk_jacobi3_2d_zero_f64(G, &A->gf, A->coef, dinv, k->scale, NULL, NULL, b->dev, w->dev, NULL));
                     else if (addP) DEV(mgk_prolong_jacobi3_2d_f64(G, &A->gf, &addP->gc, A->coef, dinv, k->scale, NULL, NULL, b->dev, addUc->dev, x->dev, w->dev, NULL));
                     else DEV(mgk_jacobi3_2d_f64(G, &A->gf, A->coef, dinv, k->scale, NULL, NULL, b->dev, x->dev, w->dev, NULL));
-                    it += 2;
+                    it += 2; g_lzstat[14]++;
                 }
                 else if (it == 0 && rrA) { rr_now(rrA, rrR, rrb, rru, b, w->dev, dinv, k->scale, NULL); g_lzstat[7]++; }
                 else if (it == 0 && !k->guess_nonzero) DEV(mgk_jacobi_zero_f64(G, &A->gf, dinv, k->scale, b->dev, w->dev, NULL));
                 else if (it == 0 && addP) DEV(mgk_prolong_jacobi_f64(G, &A->gf, &addP->gc, A->coef, dinv, k->scale, b->dev, addUc->dev, x->dev, w->dev, NULL));
                 else if (A->gf.dim == 2 && maxit - it >= 2 && A->gf.nx >= pair_min_n) {
                     DEV(mgk_jacobi2_2d_f64(G, &A->gf, A->coef, dinv, k->scale, b->dev, x->dev, w->dev, NULL));
-                    it++;
+                    it++; g_lzstat[15]++;
                 } else DEV(mgk_jacobi_f64(G, &A->gf, A->coef, dinv, k->scale, b->dev, x->dev, w->dev, NULL));
                 swap_dev(x, w);
             }
@@ -2169,7 +2184,7 @@ PetscErrorCode KSPSolve(KSP k, Vec b, Vec x) {
                 if (rrA || !k->guess_nonzero) DEV(mgk_jacobi3_2d_zero_f64(G, &A->gf, NULL, 1.0, k->scale, A->d_ctab, dt, b->dev, w->dev, NULL));
                 else if (addP) DEV(mgk_prolong_jacobi3_2d_f64(G, &A->gf, &addP->gc, NULL, 1.0, k->scale, A->d_ctab, dt, b->dev, addUc->dev, x->dev, w->dev, NULL));
                 else DEV(mgk_jacobi3_2d_f64(G, &A->gf, NULL, 1.0, k->scale, A->d_ctab, dt, b->dev, x->dev, w->dev, NULL));
-                it += 2;
+                it += 2; g_lzstat[14]++;
             }
             else if (it == 0 && rrA) { rr_now(rrA, rrR, rrb, rru, b, w->dev, 1.0, k->scale, dt); g_lzstat[7]++; }
             else if (it == 0 && !k->guess_nonzero) DEV(mgk_jacobi_zero_rowcoef_f64(G, &A->gf, dt, k->scale, b->dev, w->dev, NULL));
@@ -2241,7 +2256,7 @@ static int norm_of_deferred_residual(Vec r, double *ss) {
         }
         k->spec_n = 3;
         k->spec_ok = 1; k->spec_b = b; k->spec_x = u; k->spec_vb = b->ver; k->spec_vx = u->ver; k->spec_epoch = g_mat_epoch;
-        g_lzstat[9]++;
+        g_lzstat[9]++; g_lzstat[14]++;
         return 1;
     }
     lz_before_write(r, 1);                                   /* r is computed by the pass below */
@@ -2259,7 +2274,7 @@ static int norm_of_deferred_residual(Vec r, double *ss) {
     }
     k->spec_n = three ? 3 : 1;
     k->spec_ok = 1; k->spec_b = b; k->spec_x = u; k->spec_vb = b->ver; k->spec_vx = u->ver; k->spec_epoch = g_mat_epoch;
-    g_lzstat[6]++;
+    g_lzstat[6]++; if (three) g_lzstat[14]++;
     return 1;
 }
 PetscErrorCode KSPView(KSP k, PetscViewer viewer) {               /* src/solver.c:1562 */

@@ -968,9 +968,19 @@ FLAT(mgk_flat_scale, (mgk_ctx *c, long n, double a, double *z, void *), z[q] = a
 FLAT(mgk_flat_pointwise_mult, (mgk_ctx *c, long n, const double *x, const double *y, double *z, void *), z[q] = x[q] * y[q])
 int mgk_flat_dot(mgk_ctx *c, long n, const double *x, const double *y, double *out, void *) {
     if (!c || !x || !y || !out) return fail(MGK_EINVAL, "mgk_flat_dot");
+    // fixed-order partial sums: one per block of 4096 entries, added up in block order -- the same bits whatever the thread count
+    // (an OpenMP reduction(+) combines the threads' sums in an order of its own: rData.dat moved by an ulp between runs)
+    const long BLK = 4096, nblk = (n + BLK - 1) / BLK;
+    std::vector<long double> part((size_t)(nblk > 0 ? nblk : 0));
+    _Pragma("omp parallel for schedule(static)")
+    for (long bq = 0; bq < nblk; bq++) {
+        long double sb = 0;
+        const long q1 = (bq + 1) * BLK < n ? (bq + 1) * BLK : n;
+        for (long q = bq * BLK; q < q1; q++) sb += (long double)x[q] * y[q];
+        part[(size_t)bq] = sb;
+    }
     long double s = 0;
-    _Pragma("omp parallel for schedule(static) reduction(+:s)")
-    for (long q = 0; q < n; q++) s += (long double)x[q] * y[q];
+    for (long bq = 0; bq < nblk; bq++) s += part[(size_t)bq];
     deliver(c, (double)s, out);
     return 0;
 }

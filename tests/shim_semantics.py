@@ -448,6 +448,91 @@ def recorded_coarse_subcycle_keeps_petsc_semantics(L, orc):
             L.MatDestroy(C.byref(m))
 
 
+def deferred_values_around_the_recorder(L, orc):
+    """two call orders the extended random programs found (both gave O(1) errors in the default mode, none with MGPETSC_TAIL=0), pinned:
+    1. a recording is open and has taken the restricted right-hand side b2; the solver of level 2 is Chebyshev, which the recorder is not
+       asked about.  Its KSPSolve makes b2 concrete: the recording is replayed call by call, and the replayed MatMult(res) defers b2 again
+       (R (b1 - A1 u1)) -- the solve read b2's buffer before the restriction had run.
+    2. a sub-cycle has run as ONE tail launch with b1 as its right-hand side; rv0 = P b1 is deferred (MatMult(pro)); b1 is overwritten
+       entirely.  The finished log takes b1's buffer and b1 continues on a spare one -- from which the deferred P b1 was then formed."""
+    from cheby_reference import cheb_steps
+    L.PetscInitialize(None, None, None, None)
+    L.PetscOptionsSetValue(None, b"-pc_type", b"jacobi")
+    L.KSPChebyshevSetEigenvalues.argtypes = [C.c_void_p, C.c_double, C.c_double]
+    npts = 33
+    A = [_dense(orc, "A", npts, l) for l in range(3)]
+    R = [_dense(orc, "R", npts, l) for l in range(2)]
+    P = [_dense(orc, "P", npts, l) for l in range(2)]
+    mA, mR, mP = [_assemble(L, a) for a in A], [_assemble(L, r) for r in R], [_assemble(L, q) for q in P]
+    d = [1.0 / np.diag(a) for a in A]
+    rng = np.random.default_rng(43)
+    b1v = rng.standard_normal(A[1].shape[0])
+
+    def vec(l):
+        v = C.c_void_p()
+        L.MatCreateVecs(mA[l], C.byref(v), None)
+        return v
+
+    def solver(l, cheby, maxit):
+        k = C.c_void_p()
+        L.KSPCreate(1, C.byref(k))
+        L.KSPSetType(k, b"chebyshev" if cheby else b"richardson"); L.KSPSetOperators(k, mA[l], mA[l]); L.KSPSetNormType(k, 0)
+        L.KSPSetTolerances(k, 1e-7, -2.0, -2.0, maxit)
+        L.KSPSetFromOptions(k)
+        L.KSPRichardsonSetScale(k, 0.8)
+        if cheby:
+            L.KSPChebyshevSetEigenvalues(k, 2.0, 0.2)
+        return k
+
+    def sweeps(l, x, rhs, m):
+        for _ in range(m):
+            x = x + 0.8 * (d[l] * (rhs - A[l] @ x))
+        return x
+
+    def close(v, want, what):
+        err = float(np.max(np.abs(_get(L, v, want.size) - want)))
+        assert err <= 1e-11 * max(1.0, float(np.abs(want).max())), (what, err)
+
+    V = C.c_void_p()
+    for cheby in (True, False):
+        rv0, b1, u1, r1, b2, u2 = vec(0), vec(1), vec(1), vec(1), vec(2), vec(2)
+        k1, k2 = solver(1, False, 2), solver(2, cheby, 3)
+        _set(L, b1, b1v)
+        L.KSPSolve(k1, b1, u1)                               # zero guess, 15^2: a recording starts
+        L.KSPSetInitialGuessNonzero(k1, 1)
+        L.KSPBuildResidual(k1, None, r1, C.byref(V))
+        L.MatMult(mR[1], V, b2)
+        L.KSPSolve(k2, b2, u2)                               # Chebyshev: interrupts the recording; Richardson: continues it
+        m_u1 = sweeps(1, np.zeros_like(b1v), b1v, 2)
+        m_b2 = R[1] @ (b1v - A[1] @ m_u1)
+        if cheby:
+            s, cs = cheb_steps(0.2, 2.0, 3)
+            pkm1, pk = np.zeros_like(m_b2), s * (d[2] * m_b2)
+            for a, w, g in cs:
+                pkm1, pk = pk, (a * pkm1 + w * pk) + g * (d[2] * (m_b2 - A[2] @ pk))
+            m_u2 = pk
+            close(u2, m_u2, "1: Chebyshev solve on the right-hand side an open recording had taken")
+            close(b2, m_b2, "1: that right-hand side")
+        else:
+            m_u2 = sweeps(2, np.zeros_like(m_b2), m_b2, 3)
+        L.MatMult(mP[1], u2, r1)
+        L.VecAXPY(u1, 1.0, r1)
+        L.KSPSolve(k1, b1, u1)                               # Richardson below: the pattern is complete, ONE tail launch
+        m_u1 = sweeps(1, m_u1 + P[1] @ m_u2, b1v, 2)
+        L.MatMult(mP[0], b1, rv0)                            # rv0 = P b1, deferred
+        L.VecSet(b1, 1.0)                                    # the finished log keeps the old b1
+        close(rv0, P[0] @ b1v, "2: P b1 deferred, then b1 overwritten while a finished log names it")
+        close(u1, m_u1, "2: u1")
+        close(u2, m_u2, "2: u2 (an unread intermediate of the tail launch)")
+        close(b2, m_b2, "2: b2 (likewise)")
+        assert np.all(_get(L, b1, b1v.size) == 1.0)
+        L.KSPDestroy(C.byref(k1)); L.KSPDestroy(C.byref(k2))
+        for v in (rv0, b1, u1, r1, b2, u2):
+            L.VecDestroy(C.byref(v))
+    for m in mA + mR + mP:
+        L.MatDestroy(C.byref(m))
+
+
 def pcmg_level_vectors_after_the_tail_launch(L, orc):
     """-cycle 8 set up as the reference does (src/solver.c:1918-1956: its own vectors handed to PCMG through PCMGSetRhs / PCMGSetX / PCMGSetR), full
     depth, PETSc's default exact coarse solve: the drop-in runs PCMG's levels from 63^2 down -- here all of them -- as ONE tail launch and does
@@ -566,84 +651,206 @@ def richardson_with_lu_is_damped_not_exact(L, orc):
     L.MatDestroy(C.byref(mA))
 
 
-def random_programs_keep_petsc_semantics(L, orc, seed=1, nprog=40, nops=60):
+MODES = {      # the drop-in's environment switches, each read once per process: one child process per mode
+    "eager": {"MGPETSC_LAZY": "0"},
+    "notail": {"MGPETSC_TAIL": "0"},
+    "lazy2": {"MGPETSC_LAZY": "2"},
+    "noj3": {"MGPETSC_J3": "0"},
+    "keepr0": {"MGPETSC_KEEP_R": "0"},
+    "round2": {"MGPETSC_J3": "0", "MGPETSC_TAIL": "0"},
+    "pairs": {"MGPETSC_PAIR_MIN_N": "7"},
+    "pairs_noj3": {"MGPETSC_PAIR_MIN_N": "7", "MGPETSC_J3": "0"},
+    "generic": {"MGPETSC_NO_RECOGNITION": "1"},
+}
+LAZY_STATS_RE = (r"lazy temporaries: (\d+) residual\+restriction passes, (\d+) prolongation sweeps fused; computed after all: (\d+) residuals, "
+                 r"(\d+) prolongations, (\d+) corrections; (\d+) dropped unread; (\d+) zero-guess sweeps out of the restriction's pass; "
+                 r"(\d+) norm passes that store r and make the next sweep, (\d+) of those sweeps adopted; "
+                 r"(\d+) norm passes that left r deferred, (\d+) of those residuals followed the old iterate into the work vector; "
+                 r"(\d+) coarse sub-cycles run as ONE tail launch, (\d+) recordings replayed call by call, (\d+) times their unread intermediates "
+                 r"were computed after all; (\d+) three-sweep passes, (\d+) two-sweep passes of KSPSolve")
+
+
+def lazy_stats(out):
+    """the sixteen counters PetscFinalize prints under MGPETSC_LAZY_STATS=1, in the order of the line: eleven of the lazy temporaries, three of
+    the tail recorder, three-sweep passes, two-sweep passes of KSPSolve"""
+    import re
+    m = re.search(LAZY_STATS_RE, out)
+    assert m, out[-1500:]
+    return [int(x) for x in m.groups()]
+
+
+def random_programs_went_the_way_of_the_mode(mode, st):
+    """st: lazy_stats() of a child that ran the extended random programs under MODES[mode] (None: no switch set).  A mode that silently ran the
+    default paths would pass every comparison with the model: the counters show that the switch switched, and that the default draw does
+    reach the recorder, the three-sweep passes and the norm pass that leaves r deferred.  (Every level is at most 63 wide: below the
+    default pairing threshold, inside the recorder's range.)"""
+    lazy, tail, three, two = st[:11], st[11:14], st[14], st[15]
+    if mode in ("eager", "generic"):                 # nothing deferred / no recognised operator to defer on
+        assert lazy == [0] * 11, (mode, st)
+    else:
+        assert lazy[0] > 0 and lazy[1] > 0, (mode, st)
+    if mode in ("eager", "notail", "round2", "lazy2", "generic"):      # (the recorder needs MGPETSC_LAZY=1)
+        assert tail == [0, 0, 0], (mode, st)
+    else:
+        assert tail[0] > 0 and tail[1] > 0, (mode, st)                 # logs that ran as one launch, and logs that were interrupted
+    assert (three == 0) == (mode in ("noj3", "round2", "pairs_noj3", "generic")), (mode, st)
+    assert (two > 0) == (mode in ("pairs", "pairs_noj3")), (mode, st)
+    if mode in ("keepr0", "lazy2", "noj3", "round2", "pairs_noj3"):    # r is left deferred only by the three-sweep norm pass, only under MGPETSC_LAZY=1
+        assert lazy[9] == 0, (mode, st)
+    if mode in (None, "notail", "pairs"):
+        assert lazy[9] > 0, (mode, st)
+    if mode == "lazy2":                              # b_c is not deferred: no coarse sweep out of the restriction's pass, no norm pass with a sweep
+        assert lazy[6] == 0 and lazy[7] == 0, (mode, st)
+
+
+def random_programs_keep_petsc_semantics(L, orc, seed=1, nprog=40, nops=60, extended=False):
     """Programs of PETSc calls drawn at random over a two-level set-up (fine / coarse 5-point operators, full weighting, bilinear prolongation,
     two Richardson + Jacobi solvers, six fine and three coarse vectors) against a numpy model that executes call by call: residuals, transfers,
     corrections, BLAS-1, norms, solves with changing max_it / scale / guess flag, reads, destroy + re-create -- with the fragments of the
     reference's loop (src/solver.c:1531-1546) among the draws, so that the drop-in's deferred temporaries, speculative sweeps and fused passes
     start and are then interrupted wherever the draw says.  Every value read, every norm and every vector at the end of a program must be what
-    call-by-call execution gives (tolerance: 1e-11 of a running magnitude bound of the vector; the arithmetic order differs from numpy's)."""
+    call-by-call execution gives (tolerance: 1e-11 of a running magnitude bound of the vector; the arithmetic order differs from numpy's).
+
+    extended: each program also draws its depth (2 or 3 levels, three more vectors on the third; transfers, frag_down and frag_up act between
+    an adjacent pair, frag_cycle is the whole cycle of that depth -- half of the time with the solvers brought to one damping factor and one
+    sweep count and the guess flags set as the reference sets them, so that the recorder's pattern completes), its operator (the uniform
+    stencil, or a row table with W != E on every level: tests/coef_cases.py) and the type of each solver (Richardson, or Chebyshev with
+    eigenvalue bounds drawn once per solver; model: the restarted recurrence of tests/cheby_reference.py, whose first step is taken at
+    max_it = 0 too; its magnitude bound grows by |c_km1| + |c_k| and |c_z| per step).  With MGPETSC_NO_RECOGNITION set every solver is
+    Richardson: the drop-in refuses Chebyshev on an assembled AIJ operator.  Not extended: the draw is call for call what it was.
+    Returns the largest error-to-bound ratio met (1.0 is the tolerance)."""
+    import os
+    from cheby_reference import EIGS, cheb_steps
+    from coef_cases import distinct_row_tables
     L.PetscInitialize(None, None, None, None)
     L.PetscOptionsSetValue(None, b"-pc_type", b"jacobi")
+    L.KSPChebyshevSetEigenvalues.argtypes = [C.c_void_p, C.c_double, C.c_double]
     rng = np.random.default_rng(seed)
+    no_cheby = bool(os.environ.get("MGPETSC_NO_RECOGNITION"))
+    worst = [0.0]
     for prog in range(nprog):
         npts = int(rng.choice([17, 33, 33, 65]))
-        A0, A1, P, R = _dense(orc, "A", npts, 0), _dense(orc, "A", npts, 1), _dense(orc, "P", npts, 0), _dense(orc, "R", npts, 0)
-        mA0, mA1, mP, mR = _assemble(L, A0), _assemble(L, A1), _assemble(L, P), _assemble(L, R)
-        nf, nc = A0.shape[0], A1.shape[0]
-        amax = {0: 5.0 * np.abs(A0).max(), 1: 5.0 * np.abs(A1).max()}
-        dinv = {0: 1.0 / np.diag(A0), 1: 1.0 / np.diag(A1)}
-        Aop = {0: A0, 1: A1}
-        fine, coarse = ["x", "b", "r", "rv", "u", "w"], ["uc", "bc", "rc"]
-        lev = {**{v: 0 for v in fine}, **{v: 1 for v in coarse}}
+        depth, rows = 2, False
+        if extended:
+            depth, rows = int(rng.integers(2, 4)), bool(rng.integers(0, 2))
+        Rl = [_dense(orc, "R", npts, l) for l in range(depth - 1)]
+        Pl = [_dense(orc, "P", npts, l) for l in range(depth - 1)]
+        if rows:
+            width = [(npts - 1) // 2 ** l - 1 for l in range(depth)]
+            Al = [_five_point(n_, (lambda ct: lambda i: ct[i])(distinct_row_tables(rng, n_)[0])) for n_ in width]
+        else:
+            Al = [_dense(orc, "A", npts, l) for l in range(depth)]
+        mAl, mPl, mRl = [_assemble(L, a) for a in Al], [_assemble(L, p_) for p_ in Pl], [_assemble(L, r_) for r_ in Rl]
+        size = [a.shape[0] for a in Al]
+        amax = {l: 5.0 * np.abs(Al[l]).max() for l in range(depth)}
+        dinv = {l: 1.0 / np.diag(Al[l]) for l in range(depth)}
+        dmax = {l: float(np.abs(dinv[l]).max()) if rows else float(dinv[l].max()) for l in range(depth)}
+        Aop = dict(enumerate(Al))
+        pools = [["x", "b", "r", "rv", "u", "w"], ["uc", "bc", "rc"], ["ud", "bd", "rd"]][:depth]
+        allv = [v for pool in pools for v in pool]
+        lev = {v: l for l, pool in enumerate(pools) for v in pool}
         H, M, mag = {}, {}, {}
-        first_f, first_c = C.c_void_p(), C.c_void_p()
-        L.MatCreateVecs(mA0, C.byref(first_f), None)
-        L.MatCreateVecs(mA1, C.byref(first_c), None)
-        for v in fine + coarse:
+        first = [C.c_void_p() for _ in range(depth)]
+        for l in range(depth):
+            L.MatCreateVecs(mAl[l], C.byref(first[l]), None)
+        for v in allv:
             h = C.c_void_p()
-            L.VecDuplicate(first_f if lev[v] == 0 else first_c, C.byref(h))
+            L.VecDuplicate(first[lev[v]], C.byref(h))
             H[v] = h
-            M[v] = rng.standard_normal(nf if lev[v] == 0 else nc)
+            M[v] = rng.standard_normal(size[lev[v]])
             mag[v] = float(np.abs(M[v]).max())
             _set(L, h, M[v])
         K, kst = {}, {}
-        for q, mat in ((0, mA0), (1, mA1)):
+        for q in range(depth):
             k = C.c_void_p()
             L.KSPCreate(1, C.byref(k))
-            L.KSPSetType(k, b"richardson"); L.KSPSetOperators(k, mat, mat); L.KSPSetNormType(k, 0)
-            kst[q] = {"maxit": int(rng.integers(0, 5)), "scale": float(rng.choice([0.5, 0.8, 1.0])), "guess": int(rng.integers(0, 2)), "b": None, "x": None}
+            kst[q] = {"maxit": int(rng.integers(0, 5)), "scale": float(rng.choice([0.5, 0.8, 1.0])), "guess": int(rng.integers(0, 2)), "b": None, "x": None,
+                      "cheby": None}
+            if extended and not no_cheby and rng.integers(0, 2):
+                kst[q]["cheby"] = EIGS[int(rng.integers(0, len(EIGS)))]
+            L.KSPSetType(k, b"chebyshev" if kst[q]["cheby"] else b"richardson"); L.KSPSetOperators(k, mAl[q], mAl[q]); L.KSPSetNormType(k, 0)
             L.KSPSetTolerances(k, 1e-7, -2.0, -2.0, kst[q]["maxit"])
             L.KSPSetFromOptions(k)
             L.KSPRichardsonSetScale(k, kst[q]["scale"])
+            if kst[q]["cheby"]:
+                L.KSPChebyshevSetEigenvalues(k, kst[q]["cheby"][1], kst[q]["cheby"][0])
             L.KSPSetInitialGuessNonzero(k, kst[q]["guess"])
             K[q] = k
         trace = []
 
         def pick(level, n=1, exclude=()):
-            pool = [v for v in (fine if level == 0 else coarse) if v not in exclude]
+            pool = [v for v in pools[level] if v not in exclude]
             return [str(t) for t in rng.choice(pool, size=n, replace=False)]
 
+        def pair():                              # the finer level of an adjacent pair
+            return int(rng.integers(0, depth - 1)) if depth > 2 else 0
+
         def check(v, what):
-            n = nf if lev[v] == 0 else nc
-            got = _get(L, H[v], n)
+            got = _get(L, H[v], size[lev[v]])
             err = float(np.max(np.abs(got - M[v])))
+            worst[0] = max(worst[0], err / (1e-11 * max(mag[v], 1e-30) + 1e-300))
             assert err <= 1e-11 * max(mag[v], 1e-30) + 1e-300, (f"seed {seed} program {prog}: {what} of {v}: error {err:.3e} against magnitude {mag[v]:.3e}", trace)
+
+        def check_norm(v, what):
+            val = C.c_double()
+            L.VecNorm(H[v], NORM_2, C.byref(val))
+            bound = 1e-11 * np.sqrt(M[v].size) * max(mag[v], 1e-30) + 1e-300
+            worst[0] = max(worst[0], abs(val.value - np.linalg.norm(M[v])) / bound)
+            assert abs(val.value - np.linalg.norm(M[v])) <= bound, (f"seed {seed} program {prog}: {what}: {val.value!r} against {np.linalg.norm(M[v])!r}", trace)
 
         def residual(q, bn, xn, rn_, via_ksp):
             if via_ksp:
                 V = C.c_void_p()
                 L.KSPBuildResidual(K[q], None, H[rn_], C.byref(V))
             else:
-                L.MatResidual(mA0 if q == 0 else mA1, H[bn], H[xn], H[rn_])
+                L.MatResidual(mAl[q], H[bn], H[xn], H[rn_])
             M[rn_] = M[bn] - Aop[q] @ M[xn]
             mag[rn_] = mag[bn] + amax[q] * mag[xn]
+
+        def restrict(l, f, c):
+            L.MatMult(mRl[l], H[f], H[c]); M[c] = Rl[l] @ M[f]; mag[c] = mag[f]
+
+        def prolong(l, c, f):
+            L.MatMult(mPl[l], H[c], H[f]); M[f] = Pl[l] @ M[c]; mag[f] = mag[c]
+
+        def correct(u_, rv_):
+            L.VecAXPY(H[u_], 1.0, H[rv_]); M[u_] = M[u_] + M[rv_]; mag[u_] = mag[u_] + mag[rv_]
 
         def solve(q, bn, xn):
             st = kst[q]
             L.KSPSolve(K[q], H[bn], H[xn])
             xm = M[xn].copy() if st["guess"] else np.zeros_like(M[xn])
             mg = mag[xn] if st["guess"] else 0.0
-            for _ in range(st["maxit"]):
-                xm = xm + st["scale"] * (dinv[q] * (M[bn] - Aop[q] @ xm))
-                mg = mg + st["scale"] * float(dinv[q].max()) * (mag[bn] + amax[q] * mg)
+            if st["cheby"]:
+                s, cs = cheb_steps(st["cheby"][0], st["cheby"][1], max(st["maxit"], 1))
+                pkm1, mkm1 = xm, mg
+                pk = pkm1 + s * (dinv[q] * (M[bn] - Aop[q] @ pkm1))
+                mk = mkm1 + s * dmax[q] * (mag[bn] + amax[q] * mkm1)
+                for c_km1, c_k, c_z in cs:
+                    z = dinv[q] * (M[bn] - Aop[q] @ pk)
+                    pkm1, pk = pk, (c_km1 * pkm1 + c_k * pk) + c_z * z
+                    mkm1, mk = mk, abs(c_km1) * mkm1 + abs(c_k) * mk + abs(c_z) * dmax[q] * (mag[bn] + amax[q] * mk)
+                xm, mg = pk, mk
+            else:
+                for _ in range(st["maxit"]):
+                    xm = xm + st["scale"] * (dinv[q] * (M[bn] - Aop[q] @ xm))
+                    mg = mg + st["scale"] * dmax[q] * (mag[bn] + amax[q] * mg)
             M[xn], mag[xn] = xm, max(mg, float(np.abs(xm).max()))
             st["b"], st["x"] = bn, xn
+
+        def param(q, what, value):
+            kst[q][what] = value
+            if what == "maxit":
+                L.KSPSetTolerances(K[q], 1e-7, -2.0, -2.0, value)
+            elif what == "scale":
+                L.KSPRichardsonSetScale(K[q], value)
+            else:
+                L.KSPSetInitialGuessNonzero(K[q], value)
 
         for step in range(nops):
             op = str(rng.choice(["resid", "kresid", "restrict", "prolong", "apply", "axpy", "scale", "set", "copy", "norm", "solve", "solve", "param", "read",
                                  "recreate", "frag_down", "frag_up", "frag_up", "frag_norm", "frag_norm", "frag_cycle"]))
-            q = int(rng.integers(0, 2))
+            q = int(rng.integers(0, depth))
             if op == "resid":
                 bn, xn, rn_ = pick(q, 3)
                 trace.append(f"MatResidual(A{q}, {bn}, {xn}, {rn_})")
@@ -655,17 +862,19 @@ def random_programs_keep_petsc_semantics(L, orc, seed=1, nprog=40, nops=60):
                 trace.append(f"KSPBuildResidual(k{q}, {rn_})   [b={kst[q]['b']}, x={kst[q]['x']}]")
                 residual(q, kst[q]["b"], kst[q]["x"], rn_, True)
             elif op == "restrict":
-                (f,), (c,) = pick(0), pick(1)
-                trace.append(f"MatMult(R, {f}, {c})")
-                L.MatMult(mR, H[f], H[c]); M[c] = R @ M[f]; mag[c] = mag[f]
+                l = pair()
+                (f,), (c,) = pick(l), pick(l + 1)
+                trace.append(f"MatMult(R{l}, {f}, {c})")
+                restrict(l, f, c)
             elif op == "prolong":
-                (f,), (c,) = pick(0), pick(1)
-                trace.append(f"MatMult(P, {c}, {f})")
-                L.MatMult(mP, H[c], H[f]); M[f] = P @ M[c]; mag[f] = mag[c]
+                l = pair()
+                (f,), (c,) = pick(l), pick(l + 1)
+                trace.append(f"MatMult(P{l}, {c}, {f})")
+                prolong(l, c, f)
             elif op == "apply":
                 a, bb = pick(q, 2)
                 trace.append(f"MatMult(A{q}, {a}, {bb})")
-                L.MatMult(mA0 if q == 0 else mA1, H[a], H[bb]); M[bb] = Aop[q] @ M[a]; mag[bb] = amax[q] * mag[a]
+                L.MatMult(mAl[q], H[a], H[bb]); M[bb] = Aop[q] @ M[a]; mag[bb] = amax[q] * mag[a]
             elif op == "axpy":
                 y, xx = pick(q, 2)
                 al = float(rng.choice([1.0, -1.0, 0.5, 2.0]))
@@ -688,24 +897,19 @@ def random_programs_keep_petsc_semantics(L, orc, seed=1, nprog=40, nops=60):
             elif op == "norm":
                 (v,) = pick(q)
                 trace.append(f"VecNorm({v})")
-                val = C.c_double()
-                L.VecNorm(H[v], NORM_2, C.byref(val))
-                assert abs(val.value - np.linalg.norm(M[v])) <= 1e-11 * np.sqrt(M[v].size) * max(mag[v], 1e-30) + 1e-300, (f"seed {seed} program {prog}: norm of {v}", trace)
+                check_norm(v, f"norm of {v}")
             elif op == "solve":
                 bn, xn = pick(q, 2)
-                trace.append(f"KSPSolve(k{q}, {bn}, {xn})   [max_it={kst[q]['maxit']} scale={kst[q]['scale']} guess={kst[q]['guess']}]")
+                trace.append(f"KSPSolve(k{q}, {bn}, {xn})   [max_it={kst[q]['maxit']} scale={kst[q]['scale']} guess={kst[q]['guess']} cheby={kst[q]['cheby']}]")
                 solve(q, bn, xn)
             elif op == "param":
                 what = str(rng.choice(["maxit", "scale", "guess"]))
                 if what == "maxit":
-                    kst[q]["maxit"] = int(rng.integers(0, 5))
-                    L.KSPSetTolerances(K[q], 1e-7, -2.0, -2.0, kst[q]["maxit"])
+                    param(q, "maxit", int(rng.integers(0, 5)))
                 elif what == "scale":
-                    kst[q]["scale"] = float(rng.choice([0.5, 0.8, 1.0]))
-                    L.KSPRichardsonSetScale(K[q], kst[q]["scale"])
+                    param(q, "scale", float(rng.choice([0.5, 0.8, 1.0])))
                 else:
-                    kst[q]["guess"] = int(rng.integers(0, 2))
-                    L.KSPSetInitialGuessNonzero(K[q], kst[q]["guess"])
+                    param(q, "guess", int(rng.integers(0, 2)))
                 trace.append(f"k{q}.{what} = {kst[q][what]}")
             elif op == "read":
                 (v,) = pick(q)
@@ -716,66 +920,83 @@ def random_programs_keep_petsc_semantics(L, orc, seed=1, nprog=40, nops=60):
                 trace.append(f"VecDestroy({v}); VecDuplicate; VecSet(1.5)")
                 L.VecDestroy(C.byref(H[v]))
                 h = C.c_void_p()
-                L.VecDuplicate(first_f if q == 0 else first_c, C.byref(h))
+                L.VecDuplicate(first[q], C.byref(h))
                 H[v] = h
                 L.VecSet(h, 1.5); M[v] = np.full_like(M[v], 1.5); mag[v] = 1.5
             elif op == "frag_down":          # src/solver.c:1534-1536
-                if kst[0]["b"] is None:
+                l = pair()
+                if kst[l]["b"] is None:
                     continue
-                (rn_,) = pick(0, 1, exclude=(kst[0]["b"], kst[0]["x"]))
-                bc_, uc_ = pick(1, 2)
-                trace.append(f"down: KSPBuildResidual(k0, {rn_}); MatMult(R, {rn_}, {bc_}); KSPSolve(k1, {bc_}, {uc_})")
-                residual(0, kst[0]["b"], kst[0]["x"], rn_, True)
-                L.MatMult(mR, H[rn_], H[bc_]); M[bc_] = R @ M[rn_]; mag[bc_] = mag[rn_]
-                solve(1, bc_, uc_)
+                (rn_,) = pick(l, 1, exclude=(kst[l]["b"], kst[l]["x"]))
+                bc_, uc_ = pick(l + 1, 2)
+                trace.append(f"down: KSPBuildResidual(k{l}, {rn_}); MatMult(R{l}, {rn_}, {bc_}); KSPSolve(k{l + 1}, {bc_}, {uc_})")
+                residual(l, kst[l]["b"], kst[l]["x"], rn_, True)
+                restrict(l, rn_, bc_)
+                solve(l + 1, bc_, uc_)
             elif op == "frag_up":            # :1540-1542
-                (uc_,) = pick(1)
-                rv_, u_, b_ = pick(0, 3)
-                if kst[0]["x"] is not None and rng.integers(0, 2):
-                    u_, b_ = kst[0]["x"], kst[0]["b"]
+                l = pair()
+                (uc_,) = pick(l + 1)
+                rv_, u_, b_ = pick(l, 3)
+                if kst[l]["x"] is not None and rng.integers(0, 2):
+                    u_, b_ = kst[l]["x"], kst[l]["b"]
                     if rv_ in (u_, b_):
-                        (rv_,) = pick(0, 1, exclude=(u_, b_))
-                trace.append(f"up: MatMult(P, {uc_}, {rv_}); VecAXPY({u_}, 1, {rv_}); KSPSolve(k0, {b_}, {u_})")
-                L.MatMult(mP, H[uc_], H[rv_]); M[rv_] = P @ M[uc_]; mag[rv_] = mag[uc_]
-                L.VecAXPY(H[u_], 1.0, H[rv_]); M[u_] = M[u_] + M[rv_]; mag[u_] = mag[u_] + mag[rv_]
-                solve(0, b_, u_)
+                        (rv_,) = pick(l, 1, exclude=(u_, b_))
+                trace.append(f"up: MatMult(P{l}, {uc_}, {rv_}); VecAXPY({u_}, 1, {rv_}); KSPSolve(k{l}, {b_}, {u_})")
+                prolong(l, uc_, rv_)
+                correct(u_, rv_)
+                solve(l, b_, u_)
             elif op == "frag_norm":          # :1545-1546 and the next :1531
-                if kst[0]["b"] is None:
+                l = int(rng.integers(0, depth)) if extended else 0
+                if kst[l]["b"] is None:
                     continue
-                (rn_,) = pick(0, 1, exclude=(kst[0]["b"], kst[0]["x"]))
-                trace.append(f"norm: KSPBuildResidual(k0, {rn_}); VecNorm({rn_})" + ("; KSPSolve(k0, same b, same x)" if step % 2 else ""))
-                residual(0, kst[0]["b"], kst[0]["x"], rn_, True)
-                val = C.c_double()
-                L.VecNorm(H[rn_], NORM_2, C.byref(val))
-                assert abs(val.value - np.linalg.norm(M[rn_])) <= 1e-11 * np.sqrt(nf) * max(mag[rn_], 1e-30) + 1e-300, (f"seed {seed} program {prog}: residual norm", trace)
+                (rn_,) = pick(l, 1, exclude=(kst[l]["b"], kst[l]["x"]))
+                trace.append(f"norm: KSPBuildResidual(k{l}, {rn_}); VecNorm({rn_})" + (f"; KSPSolve(k{l}, same b, same x)" if step % 2 else ""))
+                residual(l, kst[l]["b"], kst[l]["x"], rn_, True)
+                check_norm(rn_, "residual norm")
                 if step % 2:
-                    solve(0, kst[0]["b"], kst[0]["x"])
-            elif op == "frag_cycle":         # one whole two-level cycle of the reference's loop on fixed vectors
-                trace.append("cycle: KSPSolve(k0,b,u); KSPBuildResidual(k0,r); MatMult(R,r,bc); KSPSolve(k1,bc,uc); MatMult(P,uc,rv); VecAXPY(u,1,rv); KSPSolve(k0,b,u); "
-                             "KSPBuildResidual(k0,r); VecNorm(r)")
+                    solve(l, kst[l]["b"], kst[l]["x"])
+            elif op == "frag_cycle":         # one whole cycle of the reference's loop over every level of the program, on fixed vectors
+                U, B, RES, COR = ["u", "uc", "ud"], ["b", "bc", "bd"], ["r", "rc"], ["rv", "rc"]     # (below level 0 r and rv are one vector, as in the reference)
+                ref_flags = bool(extended and rng.integers(0, 2))
+                trace.append(f"cycle over {depth} levels: KSPSolve(k0,b,u); down {{KSPBuildResidual; MatMult(R); KSPSolve}}; up {{MatMult(P); VecAXPY; KSPSolve}}; "
+                             "KSPBuildResidual(k0,r); VecNorm(r)" + (" -- one scale, one max_it, the guess flags of src/solver.c:1532-1543" if ref_flags else ""))
+                if ref_flags:
+                    sc, v0 = float(rng.choice([0.5, 0.8, 1.0])), int(rng.integers(1, 5))
+                    for l in range(depth):
+                        param(l, "scale", sc)
+                        param(l, "maxit", v0 if l < depth - 1 else int(rng.integers(1, 5)))
+                        param(l, "guess", int(rng.integers(0, 2)) if l == 0 else 0)
+                trace.append("   with " + "; ".join(f"k{l}: max_it={kst[l]['maxit']} scale={kst[l]['scale']} guess={kst[l]['guess']} cheby={kst[l]['cheby']}" for l in range(depth)))
                 solve(0, "b", "u")
+                if ref_flags:
+                    param(0, "guess", 1)
+                for l in range(1, depth):
+                    residual(l - 1, B[l - 1], U[l - 1], RES[l - 1], True)
+                    restrict(l - 1, RES[l - 1], B[l])
+                    solve(l, B[l], U[l])
+                    if ref_flags and l != depth - 1:
+                        param(l, "guess", 1)
+                for l in range(depth - 2, -1, -1):
+                    prolong(l, U[l + 1], COR[l])
+                    correct(U[l], COR[l])
+                    solve(l, B[l], U[l])
+                    if ref_flags and l != 0:
+                        param(l, "guess", 0)
                 residual(0, "b", "u", "r", True)
-                L.MatMult(mR, H["r"], H["bc"]); M["bc"] = R @ M["r"]; mag["bc"] = mag["r"]
-                solve(1, "bc", "uc")
-                L.MatMult(mP, H["uc"], H["rv"]); M["rv"] = P @ M["uc"]; mag["rv"] = mag["uc"]
-                L.VecAXPY(H["u"], 1.0, H["rv"]); M["u"] = M["u"] + M["rv"]; mag["u"] = mag["u"] + mag["rv"]
-                solve(0, "b", "u")
-                residual(0, "b", "u", "r", True)
-                val = C.c_double()
-                L.VecNorm(H["r"], NORM_2, C.byref(val))
-                assert abs(val.value - np.linalg.norm(M["r"])) <= 1e-11 * np.sqrt(nf) * max(mag["r"], 1e-30) + 1e-300, (f"seed {seed} program {prog}: cycle norm", trace)
+                check_norm("r", "cycle norm")
             if max(mag.values()) > 1e200:        # (a draw that keeps multiplying by A: start the next program)
                 break
-        for v in fine + coarse:
+        for v in allv:
             check(v, "final value")
-        for q in (0, 1):
+        for q in range(depth):
             L.KSPDestroy(C.byref(K[q]))
-        for v in fine + coarse:
+        for v in allv:
             L.VecDestroy(C.byref(H[v]))
-        L.VecDestroy(C.byref(first_f)); L.VecDestroy(C.byref(first_c))
-        for m in (mA0, mA1, mP, mR):
+        for h in first:
+            L.VecDestroy(C.byref(h))
+        for m in mAl + mPl + mRl:
             L.MatDestroy(C.byref(m))
-    import os
+    print(f"random programs (seed {seed}, {nprog} programs{', extended draw' if extended else ''}): largest error / bound = {worst[0]:.3e}")
     if os.environ.get("MGPETSC_LAZY_STATS"):       # which of the drop-in's fast paths the draws went through (printed by PetscFinalize)
         L.PetscFinalize.argtypes = []
         L.PetscFinalize()
@@ -1038,9 +1259,10 @@ if __name__ == "__main__":      # python tests/shim_semantics.py <shared library
     from oracle import Oracle
     lib = type_shim(C.CDLL(sys.argv[1], mode=os.RTLD_LOCAL))
     {"lazy": lazy_temporaries_keep_petsc_semantics, "spec": speculative_sweep_is_adopted_only_when_nothing_changed,
-     "keepr": residual_left_deferred_by_the_norm_pass, "tailrec": recorded_coarse_subcycle_keeps_petsc_semantics, "pcmgtail": pcmg_level_vectors_after_the_tail_launch, "lu": richardson_with_lu_is_damped_not_exact,
+     "keepr": residual_left_deferred_by_the_norm_pass, "tailrec": recorded_coarse_subcycle_keeps_petsc_semantics, "recorder": deferred_values_around_the_recorder, "pcmgtail": pcmg_level_vectors_after_the_tail_launch, "lu": richardson_with_lu_is_damped_not_exact,
      "nonsym": nonsymmetric_operators_keep_petsc_semantics,
      "refstreams": lambda L_, o_: print("reference_streams:", reference_streams(L_, __import__("ref_fixtures").load_assembly()), "comparisons"),
      "random": lambda L_, o_: random_programs_keep_petsc_semantics(L_, o_, seed=int(sys.argv[3]) if len(sys.argv) > 3 else 1,
-                                                                   nprog=int(sys.argv[4]) if len(sys.argv) > 4 else 40)}[sys.argv[2]](lib, Oracle())
+                                                                   nprog=int(sys.argv[4]) if len(sys.argv) > 4 else 40,
+                                                                   extended=len(sys.argv) > 5 and sys.argv[5] == "ext")}[sys.argv[2]](lib, Oracle())
     print("SEMANTICS_OK", sys.argv[2])
