@@ -656,6 +656,29 @@ int  mgk_xline_chunk_reduce_f64(mgk_ctx *ctx, const mgk_geom *g, int c, const do
 int  mgk_xline_chunk_correct_f64(mgk_ctx *ctx, const mgk_geom *g, int c, const double *vtab, const double *wtab, long gstride, double scale,
                                  const double *t, const double *sep, const double *u, double *unew, void *stream);
 
+/* ---- red-black Gauss-Seidel, 2-D (csrc/mg_rbgs.c; kernels in csrc/mgk_rbgs.hip) ----
+ * Point (i, j) of a level field -- 0-based interior row i, column j -- has the colour (i + j) & 1.  One sweep is two half-sweeps, colour 0
+ * first, then colour 1.  A half-sweep of colour c replaces every point of colour c by
+ *     u' = u + scale ((b - t) dinv_i),   t = the row's five-term sum in the order of mgk_rowcoef_f64 (S, W, C, E, N) over the CURRENT field,
+ * the expression of mgk_jacobi_f64 / mgk_rowcoef_f64 mode 0 restricted to one colour (no FMA, every product and sum rounded on its own); the
+ * points of the other colour pass through unchanged.  scale is the relaxation factor; 1 is plain Gauss-Seidel.
+ *   mgk_rbgs_2d_f64           unew = RB^nsweeps(u)                                                        24 B per unknown, either nsweeps
+ *                             u == NULL: the zero guess -- the same expression on a zeroed field, u is not read                       16 B
+ *   mgk_prolong_rbgs_2d_f64   unew = RB^nsweeps(u + P uc): the correction is added when a row is first touched, in the arithmetic of
+ *                             mgk_prolong_add_f64 (parents in ascending coarse index)                                                  25 B
+ * nsweeps is 1 (two stages in one pass) or 2 (four stages).  k5 / dinv: the level's five constants {(i-1), W, C, E, (i+1)} and 1 / diag (the
+ * coef / dinv of mgk_jacobi3_2d_f64); or atab / itab != NULL: per-row tables, ny x 5 coefficients and ny inverse diagonals (stretched meshes:
+ * the ctab / dtab of the *_rowcoef_* entry points, named as the line passes name theirs; k5 may then be NULL).  The ghost ring is read as
+ * zeros and, like the padding, never written.  Any 2-D grid.  MGK_EINVAL: nsweeps other than 1 or 2, unew == u, unew == b, a NULL u in the
+ * prolongation form, a coarse grid that does not match.  Stores: by size (ordinary within the 256 MB Infinity Cache, non-temporal above);
+ * mgk_set_tuning(variant = 0 / 1) forces one policy, and its second argument, > 0, is the length of a y chunk in rows (rounded up to even;
+ * default: at least 12). */
+int  mgk_rbgs_2d_f64(mgk_ctx *ctx, const mgk_geom *g, const double *k5, double dinv, double scale, const double *atab, const double *itab,
+                     int nsweeps, const double *b, const double *u, double *unew, void *stream);
+int  mgk_prolong_rbgs_2d_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom *gc, const double *k5, double dinv, double scale,
+                             const double *atab, const double *itab, int nsweeps, const double *b, const double *uc, const double *u,
+                             double *unew, void *stream);
+
 /* Named values of mgk_set_tuning's first argument.  From 30 up a value selects ONE form of ONE launcher (every other launcher takes it as
  * "no special form"); the values below 30 are read three ways, see the table under the enum.  MGK_TUNE_STORE_* name the 0 / 1 reading of
  * the Krylov and line passes.  mgk_set_tuning takes any int: a value nothing reads selects nothing. */

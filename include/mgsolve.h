@@ -20,7 +20,7 @@ extern "C" {
 
 typedef enum { MG_KSP_RICHARDSON = 0, MG_KSP_CHEBYSHEV = 1 } mg_ksp_type;
 typedef enum { MG_PREC_FP64 = 0, MG_PREC_MIXED = 1 } mg_precision;
-typedef enum { MG_PC_JACOBI = 0, MG_PC_LINE_Y = 1, MG_PC_LINE_X = 2, MG_PC_LINE_ALT = 3 } mg_pc_type;
+typedef enum { MG_PC_JACOBI = 0, MG_PC_LINE_Y = 1, MG_PC_LINE_X = 2, MG_PC_LINE_ALT = 3, MG_PC_RBGS = 4 } mg_pc_type;
 
 /* the bits of mg_config.fuse: one fused pass (or family of passes) each.  The VALUES are ABI: tests, bench.py, the tools and
  * `mgpoisson -mg_fuse N` pass numerals.  "(bit N)" is the name the bit goes by in DESIGN.md, the tests and the profiles. */
@@ -119,7 +119,15 @@ typedef struct mg_config {
                          * line relaxation: within one smoothing (one KSPSolve of max_it sweeps, counted from 0 in every call) sweep k is a
                          * y-line sweep for even k and an x-line sweep for odd k -- the same number of sweeps as MG_PC_LINE_Y, and a cycle count
                          * independent of npts on meshes 0, 1 and 2.  Both under the conditions of MG_PC_LINE_Y, with
-                         * the same refusals */
+                         * the same refusals.
+                         * MG_PC_RBGS (4) red-black Gauss-Seidel: point (i, j) has the colour (i + j) & 1; a sweep updates
+                         * colour 0, then colour 1 from the new values, each point by the expression of point Jacobi with `scale` as the
+                         * relaxation factor.  It converges at scale 1 (PETSc's default), where the Jacobi-type smoothers need 0.8 or GMRES.
+                         * A smoothing of v sweeps is v / 2 passes of two sweeps and one of one sweep if v is odd (mgk_rbgs_2d_f64; with fuse
+                         * bit 1 the first post-smoothing pass also prolongs, mgk_prolong_rbgs_2d_f64); every pass swaps u / tmp, an even
+                         * number of times per level and cycle.  Conditions and refusals of MG_PC_LINE_Y; line_chunk, xline_chunk and
+                         * line_tail must be 0.  Fuse bits 0, 1 and 2 stay, bits 3, 5 and 8-15 are cleared; the coarse levels run by launch
+                         * inside the HIP graph */
     int line_tail;      /* (0, default: off) 1: the coarse levels of a line cycle (MG_PC_LINE_Y / _X / _ALT) whose fields fit in LDS run as ONE
                          * kernel per cycle (mgk_tail_cycle_line_f64) instead of two launches per sweep plus the
                          * transfers -- what fuse bit 9 is to point Jacobi.  Bit-identical to the launches it replaces.  The tail starts at

@@ -86,8 +86,9 @@ int main(int argc, char **argv) {
     if ((v = get("-mg_graph"))) c.graph = atoi(v);
     if ((v = get("-pc_type")) && !strcmp(v, "yline")) c.pc_type = MG_PC_LINE_Y;     /* y-line Jacobi (2-D; the remedy for -mesh 1) */
     else if (v && !strcmp(v, "altline")) c.pc_type = MG_PC_LINE_ALT;                /* y- and x-line sweeps in turn (2-D; -mesh 0, 1 and 2 alike) */
+    else if (v && !strcmp(v, "rbgs")) c.pc_type = MG_PC_RBGS;                       /* red-black Gauss-Seidel (2-D; converges at -ksp_richardson_scale 1) */
     else if (v && strcmp(v, "jacobi")) {                                            /* (x-line Jacobi alone, MG_PC_LINE_X, is offered by the library only) */
-        fprintf(stderr, "mgpoisson: only -pc_type jacobi and -pc_type yline are built, and -pc_type altline (y- and x-line sweeps in turn)\n");
+        fprintf(stderr, "mgpoisson: only -pc_type jacobi and -pc_type yline are built, -pc_type altline (y- and x-line sweeps in turn) and -pc_type rbgs (red-black Gauss-Seidel)\n");
         return 2;
     }
     if ((v = get("-xline_chunk"))) c.xline_chunk = atoi(v);                         /* the x-line sweeps in chunks of that many columns (0: whole) */

@@ -25,6 +25,7 @@ static int fmg_check(const mg_solver *s, int nu) {
     if (s->cfg.precision != MG_PREC_FP64) return mgi_fail(MGK_EINVAL, "mg_solver_fmg: built for fp64 (not mixed precision)");
     if (s->cfg.ksp_type != MG_KSP_RICHARDSON) return mgi_fail(MGK_EINVAL, "mg_solver_fmg: built for Richardson + Jacobi (not Chebyshev)");
     if (s->cfg.pc_type == MG_PC_LINE_Y) return mgi_fail(MGK_EINVAL, "mg_solver_fmg: built for point Jacobi (not the y-line smoother)");
+    if (s->cfg.pc_type == MG_PC_RBGS) return mgi_fail(MGK_EINVAL, "mg_solver_fmg: built for point Jacobi (not the red-black Gauss-Seidel smoother)");
     if (s->cfg.pc_type != MG_PC_JACOBI) return mgi_fail(MGK_EINVAL, "mg_solver_fmg: built for point Jacobi (not the x-line or alternating line smoothers)");
     if (s->cfg.mesh != 0) return mgi_fail(MGK_EINVAL, "mg_solver_fmg: built for the uniform mesh (-mesh 0)");
     if (s->levels < 2) return mgi_fail(MGK_EINVAL, "mg_solver_fmg: needs two levels or more");

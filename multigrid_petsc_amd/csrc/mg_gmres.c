@@ -33,6 +33,7 @@ static int gmres_check(const mg_solver *s, int restart) {
     if (s->cfg.precision != MG_PREC_FP64) return mgi_fail(MGK_EINVAL, "mg_solver_solve_gmres: built for fp64 (not mixed precision)");
     if (s->cfg.ksp_type != MG_KSP_RICHARDSON) return mgi_fail(MGK_EINVAL, "mg_solver_solve_gmres: built for Richardson + Jacobi (not Chebyshev)");
     if (s->cfg.pc_type == MG_PC_LINE_Y) return mgi_fail(MGK_EINVAL, "mg_solver_solve_gmres: built for point Jacobi (not the y-line smoother)");
+    if (s->cfg.pc_type == MG_PC_RBGS) return mgi_fail(MGK_EINVAL, "mg_solver_solve_gmres: built for point Jacobi (not the red-black Gauss-Seidel smoother)");
     if (s->cfg.pc_type != MG_PC_JACOBI) return mgi_fail(MGK_EINVAL, "mg_solver_solve_gmres: built for point Jacobi (not the x-line or alternating line smoothers)");
     return 0;
 }

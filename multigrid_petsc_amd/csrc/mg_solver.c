@@ -301,11 +301,12 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
     if (cfg->dim != 2 && cfg->dim != 3) return mgfail(MGK_EINVAL, "mg_solver_create: dim must be 2 or 3");
     if (cfg->levels < 1 || cfg->levels > MG_MAX_LEVELS) return mgfail(MGK_EINVAL, "mg_solver_create: bad level count");
     if (cfg->npts < 3) return mgfail(MGK_EINVAL, "mg_solver_create: npts < 3");
-    if (cfg->pc_type < MG_PC_JACOBI || cfg->pc_type > MG_PC_LINE_ALT)
-        return mgfail(MGK_EINVAL, "mg_solver_create: pc_type must be jacobi (0), yline (1), xline (2) or altline (3)");
+    if (cfg->pc_type < MG_PC_JACOBI || cfg->pc_type > MG_PC_RBGS)
+        return mgfail(MGK_EINVAL, "mg_solver_create: pc_type must be jacobi (0), yline (1), xline (2), altline (3) or rbgs (4)");
     if (cfg->pc_type != MG_PC_JACOBI) {
-        /* the line smoothers (mg_line.c, mg_xline.c): 2-D, fp64, one rank, Richardson */
-        const char *name = cfg->pc_type == MG_PC_LINE_Y ? "y-line" : cfg->pc_type == MG_PC_LINE_X ? "x-line" : "alternating line";
+        /* the line smoothers (mg_line.c, mg_xline.c) and red-black Gauss-Seidel (mg_rbgs.c): 2-D, fp64, one rank, Richardson */
+        const char *name = cfg->pc_type == MG_PC_LINE_Y ? "y-line" : cfg->pc_type == MG_PC_LINE_X ? "x-line" :
+                           cfg->pc_type == MG_PC_RBGS ? "red-black Gauss-Seidel" : "alternating line";
         const char *why = NULL;
         char msg[192];
         if (cfg->dim != 2) why = "2-D (not 3-D: that needs a plane smoother)";
@@ -316,9 +317,15 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
             snprintf(msg, sizeof(msg), "mg_solver_create: the %s smoother is built for %s", name, why);
             return mgfail(MGK_EINVAL, msg);
         }
-        if (cfg->pc_type != MG_PC_LINE_X && (!mg_line_tables || !mg_line_smooth))
+        if (cfg->pc_type == MG_PC_RBGS) {
+            if (!mg_rbgs_smooth || !mg_rbgs_prolong_smooth)
+                return mgfail(MGK_EINVAL, "mg_solver_create: this build has no red-black Gauss-Seidel smoother (mg_rbgs.c is not linked)");
+            if (cfg->line_chunk != 0 || cfg->xline_chunk != 0 || cfg->line_tail != 0)
+                return mgfail(MGK_EINVAL, "mg_solver_create: line_chunk, xline_chunk and line_tail go with the line smoothers: they must be 0 with pc_type rbgs");
+        }
+        else if (cfg->pc_type != MG_PC_LINE_X && (!mg_line_tables || !mg_line_smooth))
             return mgfail(MGK_EINVAL, "mg_solver_create: this build has no y-line smoother (mg_line.c is not linked)");
-        if (cfg->pc_type != MG_PC_LINE_Y && (!mg_xline_tables || !mg_xline_smooth))
+        if (cfg->pc_type != MG_PC_RBGS && cfg->pc_type != MG_PC_LINE_Y && (!mg_xline_tables || !mg_xline_smooth))
             return mgfail(MGK_EINVAL, "mg_solver_create: this build has no x-line smoother (mg_xline.c is not linked)");
     }
     if (cfg->line_chunk < 0 || cfg->line_chunk == 1)
@@ -367,7 +374,9 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
                                                                                       * (255^3: 0.107 ms against 2 x 0.063) */
     /* line smoothers: the passes that bake point Jacobi in are off (bits 1, 3, 5, 8-15); the fused residual + norm (0) and residual +
      * restriction (2) stay, the coarse levels run by launch inside the HIP graph */
-    if (s->cfg.pc_type != MG_PC_JACOBI) s->cfg.fuse &= ~MG_FUSE_POINT_JACOBI_PASSES;
+    /* (red-black Gauss-Seidel keeps bit 1: it has a pass of its own for the prolongation fused into the first post-smoothing pass, mg_rbgs.c) */
+    if (s->cfg.pc_type == MG_PC_RBGS) s->cfg.fuse &= ~(MG_FUSE_POINT_JACOBI_PASSES & ~MG_FUSE_PROLONG_SWEEP);
+    else if (s->cfg.pc_type != MG_PC_JACOBI) s->cfg.fuse &= ~MG_FUSE_POINT_JACOBI_PASSES;
     if (s->cfg.mesh) s->cfg.fuse &= ~MG_FUSE_NO_ROW_TABLE_FORM;   /* row-dependent coefficients (2-D, fp64): the same fused cycle on the row-table forms of the kernels */
     if (s->cfg.overlap < 0) s->cfg.overlap = 1;
     if (s->cfg.graph < 0) s->cfg.graph = 1;
@@ -864,6 +873,7 @@ static int smooth(mg_solver *s, int P, int l, int maxit, int pre) {
         mg_fset *Fl = &s->L[l].f[0];
         Fl->pre_done = 0; Fl->jz_ready = 0; Fl->last_sweep_pending = 0;
         mgi_u_rewritten(Fl);
+        if (s->cfg.pc_type == MG_PC_RBGS) return mg_rbgs_smooth(s, l, maxit);         /* (mg_rbgs.c: every pass writes tmp and swaps u / tmp) */
         return s->cfg.pc_type == MG_PC_LINE_Y ? mg_line_smooth(s, l, maxit) : mg_xline_smooth(s, l, maxit);   /* x sweeps, or y and x in turn */
     }
     if (s->cfg.ksp_type == MG_KSP_CHEBYSHEV && !j3_2d_ok(s, P, l, maxit)) return smooth_chebyshev(s, l, maxit);
@@ -1138,6 +1148,12 @@ static int prolong_smooth(mg_solver *s, int P, int l) {
     if (!(s->cfg.fuse & MG_FUSE_PROLONG_SWEEP) || (s->cfg.ksp_type != MG_KSP_RICHARDSON && !j3_2d_ok(s, P, l, v0)) || v0 < 1) {
         CHK(prolong_from(s, P, l));
         return smooth(s, P, l, v0, 0);
+    }
+    if (s->cfg.pc_type == MG_PC_RBGS) {
+        /* red-black Gauss-Seidel: the prolongation, the correction and the first one or two post-smoothing sweeps in one pass, then plain
+         * passes (mg_rbgs.c): as many swaps as the pre-smoothing made */
+        F->pre_done = 0; F->jz_ready = 0; F->last_sweep_pending = 0;
+        return mg_rbgs_prolong_smooth(s, l, v0);
     }
     if (j3_2d_ok(s, P, l, v0)) {
         /* 2-D: the prolongation, the correction and the first THREE post-smoothing sweeps in one pass */
@@ -1432,7 +1448,10 @@ gathered:
 static int coarse_part(mg_solver *s, int P, int lg) {
     const int levels = s->levels, lend = s->ltail ? s->ltail : levels - 1;     /* last level the loops below handle themselves */
     for (int l = lg; l <= lend; l++) CHK(descend(s, P, l));
-    if (!s->ltail && (s->cfg.v[1] & 1) && s->cfg.pc_type == MG_PC_JACOBI) {   /* restore the coarsest level's buffer identity (a line sweep swaps nothing) */
+    /* restore the coarsest level's buffer identity after an odd number of swaps (a line sweep swaps nothing; red-black Gauss-Seidel swaps
+     * once per pass of two sweeps, mg_rbgs.c) */
+    const int odd_swaps = s->cfg.pc_type == MG_PC_JACOBI ? (s->cfg.v[1] & 1) : s->cfg.pc_type == MG_PC_RBGS ? (((s->cfg.v[1] + 1) / 2) & 1) : 0;
+    if (!s->ltail && odd_swaps) {
         mg_fset *Cz = &s->L[levels - 1].f[P];
         CHK(mgk_d2d(s->ctx, Cz->tmp, Cz->u, (size_t)OPS[P].esz * (size_t)Cz->g.total, NULL));
         swap_ptr(&Cz->u, &Cz->tmp);

@@ -137,7 +137,11 @@ extern int mg_xline_chunk_smooth(mg_solver *s, int l, int maxit) __attribute__((
  * mgk_tail_cycle_line_f64; mg_solver.c (tail()) reaches it through a WEAK reference, and mg_solver_create refuses line_tail = 1 in a build
  * without it */
 extern int mg_line_tail(mg_solver *s) __attribute__((weak));      /* the levels ltail .. L-1 of one cycle in one kernel */
-long mg_xline_stride(int n, int uniform);                                          /* row stride of the x table (mg_xline.c) */
+/* red-black Gauss-Seidel (pc_type MG_PC_RBGS): mg_rbgs.c holds the only calls of mgk_rbgs_2d_f64 / mgk_prolong_rbgs_2d_f64, reached through WEAK
+ * references in the same way; mg_solver_create refuses the smoother in a build without it.  Every pass writes tmp and swaps u / tmp */
+extern int mg_rbgs_smooth(mg_solver *s, int l, int maxit) __attribute__((weak));   /* KSPSolve on level l: ceil(maxit / 2) passes */
+extern int mg_rbgs_prolong_smooth(mg_solver *s, int l, int maxit) __attribute__((weak));   /* u_l <- RB^maxit(u_l + P u_{l+1}), maxit >= 1: the first pass prolongs */
+long mg_xline_stride(int n, int uniform);                                         /* row stride of the x table (mg_xline.c) */
 void mg_xline_factor(int n, int rows, const double *ctab, long gs, double *g);     /* the x table on the host (mg_xline.c) */
 
 /* the steps of mg_solver.c, for mg_fmg.c (fp64, one rank) */

@@ -246,6 +246,9 @@ def _sigs(L):
         # the LDS-resident coarse levels of a line cycle in one launch: (nlev, n, pc, ctab[], ltab[], gtab[], qtab[], xgtab[], xgs[], scale, v0, v1, b, u)
         "mgk_tail_cycle_line_f64": (i, [vp, G, i, C.POINTER(i), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                         C.POINTER(C.c_long), d, i, i, vp, vp, vp]),
+        # red-black Gauss-Seidel: (coef, dinv, scale, ctab, dtab, nsweeps, b, u or None, unew) / (gf, gc, ..., nsweeps, b, uc, u, unew)
+        "mgk_rbgs_2d_f64": (i, [vp, G, c_dp, d, d, vp, vp, i, vp, vp, vp, vp]),
+        "mgk_prolong_rbgs_2d_f64": (i, [vp, G, G, c_dp, d, d, vp, vp, i, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in S.items():
         f = getattr(L, name)

@@ -48,7 +48,8 @@ class Fuse(enum.IntFlag):
 
 
 _KSP = {"richardson": 0, "chebyshev": 1}
-_PC = {"jacobi": 0, "yline": 1, "xline": 2, "altline": 3}
+_PC = {"jacobi": 0, "yline": 1, "xline": 2, "altline": 3}       # the Jacobi-type smoothers (point and line)
+_PC_GS = {"rbgs": 4}                                             # the Gauss-Seidel-type smoothers: red-black (mg_pc_type MG_PC_RBGS)
 
 
 def _lib():
@@ -166,7 +167,7 @@ class Solver:
         cfg.pair_min_n = pair_min_n
         cfg.slab_chunk = slab_chunk
         cfg.mesh = mesh
-        cfg.pc_type = _PC[pc_type]        # "yline" / "xline": y- / x-line Jacobi, "altline": y and x sweeps in turn (2-D, fp64, one rank, Richardson; include/mgsolve.h)
+        cfg.pc_type = _PC_GS[pc_type] if pc_type in _PC_GS else _PC[pc_type]      # "yline" / "xline": y- / x-line Jacobi, "altline": y and x sweeps in turn, "rbgs": red-black Gauss-Seidel (2-D, fp64, one rank, Richardson; include/mgsolve.h)
         cfg.xline_chunk = xline_chunk     # c > 0, a multiple of 16: the x-line sweeps in chunks of c columns (four passes per sweep); 0: whole
         cfg.line_chunk = line_chunk       # c >= 2: the y-line sweeps in chunks of c rows (four passes per sweep); 0: whole
         cfg.line_tail = line_tail         # 1: the LDS-resident coarse levels of a line cycle in one launch; 0: by launch
