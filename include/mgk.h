@@ -16,6 +16,10 @@
  *   - device arrays use the padded layout described by mgk_geom (below).
  *   - arithmetic: IEEE fp64, no fused multiply-add, terms summed in ascending
  *     column order of the assembled row (see DESIGN.md "canonical arithmetic").
+ *   - where a call stores: a call writes the interior of its output fields, and within an output's allocation it may
+ *     store zeros into the ghost ring and row padding.  Where they held 0 they hold 0 afterwards.  A call never writes
+ *     outside the allocation.  The slab and range forms write only the planes / rows they are given.
+ *     (tests/guarded.py pins this under the kernel tests: guard zones, a poisoned interior, a zero frame.)
  *
  * Device layout of a level field (one rank's slab)
  *   interior unknown (k,i,j), k plane (z), i row (y), j column (x):

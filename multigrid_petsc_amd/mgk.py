@@ -331,6 +331,10 @@ class Mgk:
         self._chk(self.L.mgk_geom_init_f32(C.byref(g), 3, n, n, n))
         return g
 
+    def field32(self, g32):
+        """new zero-filled padded fp32 field"""
+        return self.alloc(4 * g32.total)
+
     def to_field32(self, g32, compact):
         tmp = self.upload(np.asarray(compact, dtype=np.float64).ravel())
         f = self.alloc(4 * g32.total)

@@ -643,7 +643,7 @@ def test_tail_cycle_f32_bit_exact(mgk, orc, n0, nlev, v0, v1):
                      lambda l, r: orc.restrict32(ns[l], r),
                      lambda l, uc, uf: orc.prolong_add32(ns[l], uc, uf), v0, v1)
     g = mgk.geom32(n0)
-    db, du = mgk.to_field32(g, b0), mgk.alloc(4 * g.total)
+    db, du = mgk.to_field32(g, b0), mgk.field32(g)
     mgk._chk(mgk.L.mgk_memset0(mgk.ctx, du, 4 * g.total, None))
     nn = (C.c_int * nlev)(*ns)
     k7 = mgk.coef([v for a in As for v in a])

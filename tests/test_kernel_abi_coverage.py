@@ -27,11 +27,6 @@ EXEMPT = {
     "mgk_graph_launch": "graph replay in mg_solver.c, exercised by the solver tests",
     "mgk_graph_destroy": "graph teardown in mg_solver.c, exercised by the solver tests",
     "mgk_paced_copy": "the phantom transport's stand-in for link time (mg_comm.c), never on the product path",
-    # pack / unpack: the layout conversion under Mgk.to_field / from_field, which every bit-exact comparison goes through
-    "mgk_pack_f64": "Mgk.to_field: every fp64 field a GPU test uploads",
-    "mgk_unpack_f64": "Mgk.from_field: every fp64 field a GPU test compares",
-    "mgk_pack_f32": "Mgk.to_field32: every fp32 field a GPU test uploads",
-    "mgk_unpack_f32": "Mgk.from_field32: every fp32 field a GPU test compares",
     # profiling aids
     "mgk_debug_tail_stamps": "profiling aid (timestamps of the tail kernel's barriers, tools/tail_phases.py); off in production",
     "mgk_stream_triad_f64": "bandwidth probe of bench.py --full (STREAM triad); no result of the solver depends on it",

@@ -861,7 +861,7 @@ def test_three_sweeps_from_the_zero_guess_in_one_pass(mgk, orc, n, prec):
     else:
         g = mgk.geom32(n)
         assert mgk.L.mgk_jacobi2_zero_ok_f32(C.byref(g)) == 1
-        db, d1, d2, dout = mgk.to_field32(g, b), mgk.alloc(4 * g.total), mgk.alloc(4 * g.total), mgk.alloc(4 * g.total)
+        db, d1, d2, dout = mgk.to_field32(g, b), mgk.field32(g), mgk.field32(g), mgk.field32(g)
         for f in (d1, d2, dout):
             mgk._chk(mgk.L.mgk_memset0(mgk.ctx, f, 4 * g.total, None))
         mgk._chk(mgk.L.mgk_jacobi_zero_f32(mgk.ctx, C.byref(g), dinv, 0.8, db, d1, None))

@@ -27,7 +27,7 @@ def test_fp32_kernels_bit_exact(mgk, orc, n):
     dinv = 1.0 / As[3]
     u, b = rng.uniform(-1, 1, N).astype(np.float32), rng.uniform(-1, 1, N).astype(np.float32)
     g = mgk.geom32(n)
-    du, db, dout = mgk.to_field32(g, u), mgk.to_field32(g, b), mgk.alloc(4 * g.total)
+    du, db, dout = mgk.to_field32(g, u), mgk.to_field32(g, b), mgk.field32(g)
     coef = mgk.coef(As)
     L = mgk.L
     variants = [-1] if n < 255 else [-1, 0, 1, 2, 3]
@@ -45,7 +45,7 @@ def test_fp32_kernels_bit_exact(mgk, orc, n):
         nc = (n - 1) // 2
         gc = mgk.geom32(nc)
         uc = rng.uniform(-1, 1, nc ** 3).astype(np.float32)
-        duc, dbc = mgk.to_field32(gc, uc), mgk.alloc(4 * gc.total)
+        duc, dbc = mgk.to_field32(gc, uc), mgk.field32(gc)
         mgk._chk(L.mgk_restrict_fw_f32(mgk.ctx, C.byref(g), C.byref(gc), du, dbc, None))
         assert np.array_equal(mgk.from_field32(gc, dbc), orc.restrict32(n, u))
         mgk._chk(L.mgk_prolong_add_f32(mgk.ctx, C.byref(g), C.byref(gc), duc, du, None))
@@ -62,7 +62,7 @@ def test_bridges_fp64_fp32(mgk, orc, n):
     As = orc.level_stencil(3, n + 2, 0)[0]
     u, b = rng.uniform(-1, 1, N), rng.uniform(-1, 1, N)
     g, g32 = mgk.geom(3, n), mgk.geom32(n)
-    du, db, dr32 = mgk.to_field(g, u), mgk.to_field(g, b), mgk.alloc(4 * g32.total)
+    du, db, dr32 = mgk.to_field(g, u), mgk.to_field(g, b), mgk.field32(g32)
     ss = C.c_double()
     mgk._chk(mgk.L.mgk_residual_f64_to_f32(mgk.ctx, C.byref(g), C.byref(g32), mgk.coef(As), db, du, dr32, C.byref(ss), None))
     r = orc.residual(3, n, As, b, u)
@@ -105,7 +105,7 @@ def test_fused_residual_restrict_fp32_bit_exact(mgk, orc, nf):
     As = orc.level_stencil(3, nf + 2, 0)[0]
     u, b = rng.uniform(-1, 1, nf ** 3).astype(np.float32), rng.uniform(-1, 1, nf ** 3).astype(np.float32)
     gf, gc = mgk.geom32(nf), mgk.geom32(nc)
-    du, db, dbc = mgk.to_field32(gf, u), mgk.to_field32(gf, b), mgk.alloc(4 * gc.total)
+    du, db, dbc = mgk.to_field32(gf, u), mgk.to_field32(gf, b), mgk.field32(gc)
     want = orc.restrict32(nf, orc.residual32(nf, As, b, u))
     for zc in (-1, 5):
         mgk.L.mgk_set_tuning(-1, zc)
@@ -126,7 +126,7 @@ def test_fused_correction_and_residual_bit_exact(mgk, orc, n, variant):
     u, b, e = rng.uniform(-1, 1, N), rng.uniform(-1, 1, N), rng.uniform(-1, 1, N).astype(np.float32)
     g, g32 = mgk.geom(3, n), mgk.geom32(n)
     du, db, dun = mgk.to_field(g, u), mgk.to_field(g, b), mgk.field(g)
-    de, dr32 = mgk.to_field32(g32, e), mgk.alloc(4 * g32.total)
+    de, dr32 = mgk.to_field32(g32, e), mgk.field32(g32)
     mgk._chk(mgk.L.mgk_memset0(mgk.ctx, dr32, 4 * g32.total, None))
     ss = C.c_double()
     ucorr = u + e.astype(np.float64)
@@ -164,7 +164,7 @@ def test_two_fp32_sweeps_in_one_pass_bit_exact(mgk, orc, n):
     dinv = 1.0 / As[3]
     u, b = rng.uniform(-1, 1, n ** 3).astype(np.float32), rng.uniform(-1, 1, n ** 3).astype(np.float32)
     g = mgk.geom32(n)
-    du, db, dout = mgk.to_field32(g, u), mgk.to_field32(g, b), mgk.alloc(4 * g.total)
+    du, db, dout = mgk.to_field32(g, u), mgk.to_field32(g, b), mgk.field32(g)
     s = 6.0 / 7.0
     want = orc.jacobi32(n, As, s, b, orc.jacobi32(n, As, s, b, u))
     for var, zc in [(v, z) for v in (-1, 2) for z in (-1, 8, 13)]:

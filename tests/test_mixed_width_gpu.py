@@ -122,8 +122,7 @@ class Thin32:
 
     def out(self, coarse=False):
         g = self.gc if coarse else self.g
-        f = self.mgk.alloc(4 * g.total)
-        self.mgk._chk(self.mgk.L.mgk_memset0(self.mgk.ctx, f, 4 * g.total, None))
+        f = self.mgk.field32(g)                               # a fresh allocation is zero-filled; under tests/guarded.py its interior is poisoned
         self._own.append(f)
         return f
 
@@ -294,7 +293,7 @@ def test_bridges_at_width(mgk, orc, n, nz):
     own = [du, db, de]
 
     def f32():
-        p = mgk.alloc(4 * g32.total)
+        p = mgk.field32(g32)
         mgk._chk(L.mgk_memset0(mgk.ctx, p, 4 * g32.total, None))
         own.append(p)
         return p
@@ -392,7 +391,9 @@ def test_fp32_slab_forms(mgk, orc, n, nz, cuts):
             return p
 
         def zeros(g):
-            return up(np.zeros(g.total, np.float32))
+            f = mgk.field32(g)
+            own.append(f)
+            return f
 
         def slab(W):                                        # interior planes and both ghost planes from the whole grid
             return up(_padded32(gs, {k: W[z0 + k] for k in range(-1, nzs + 1) if 0 <= z0 + k < nz}))
