@@ -501,7 +501,9 @@ int  mgk_interp_jacobi3_2d_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom 
                                const double *b, const double *uc, double *unew, void *stream);
 
 /* the same in 3-D (whole grids, any vertex-centred shape): unew = J(J(J(u))) [and *sumsq_host = || b - A u ||^2 of the input field] in one
- * pass, 24 B per unknown.  Independent waves, one per SIMD (up to 512 registers per lane), 120 x 4 point columns per wave marching along z. */
+ * pass, 24 B per unknown.  Independent waves, one per SIMD (up to 512 registers per lane), 120 x 4 point columns per wave marching along z;
+ * on rows of 512 / 1024 (nx = 511, 1023) the stacked form of include/mgk_sweep3.h, two waves per SIMD (MGK_TUNE_J3_3D_WAVES keeps the
+ * independent waves there, MGK_TUNE_J3_3D_STACKED refuses every other shape). */
 int  mgk_jacobi3_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef, double dinv, double scale,
                      const double *b, const double *u, double *unew, void *stream);
 int  mgk_jacobi3_sumsq_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef, double dinv, double scale,
@@ -724,8 +726,11 @@ enum mgk_tune {
     MGK_TUNE_J3_3D_TY2         = 62,   /* jacobi3_3d: wave tiles of 2 rows */
     MGK_TUNE_J3_3D_TY3         = 63,   /* jacobi3_3d: wave tiles of 3 rows (what the norm form always takes) */
     MGK_TUNE_J3_3D_ROWWISE     = 64,   /* jacobi3_3d: the sweeps row by row instead of term by term over the rows */
-    MGK_TUNE_NO_EXACT_FMA      = 65    /* the fp64 3-D constant-coefficient kernels: the generic stencil sum (multiply, then add) even where all six
+    MGK_TUNE_NO_EXACT_FMA      = 65,   /* the fp64 3-D constant-coefficient kernels: the generic stencil sum (multiply, then add) even where all six
                                           off-diagonal coefficients are +-2^e, e >= 0, and the exact-FMA form would be taken (same results) */
+    MGK_TUNE_J3_3D_WAVES       = 66,   /* jacobi3_3d: the independent-wave form k_jacobi3_3d, one wave per SIMD, on rows of 512 / 1024 too */
+    MGK_TUNE_J3_3D_STACKED     = 67,   /* jacobi3_3d: the stacked form k_jacobi3s, two waves per SIMD (rows of 512 / 1024, where it is the default; other shapes refused) */
+    MGK_TUNE_J3_3D_STACKED_DISPATCH = 68   /* jacobi3_3d, jacobi3_sumsq_mid: the stacked form with its tiles in dispatch order */
 };
 
 /* tuning knobs (profiling only), per calling thread: <=0 keeps the built-in choice.  They are GLOBAL to that thread, not per kernel -- set

@@ -71,11 +71,20 @@ typedef enum mg_fuse_bits {
      * that fit in LDS as one kernel per cycle in 2-D and 3-D with any step counts (mgk_tail_cycle_cheby_f64, with bit 9); off: every
      * step is a launch of its own */
     MG_FUSE_CHEBY = 32768,
-    /* what mg_config.fuse = -1 selects: bits 0-5 and 8-15 */
+    /* bits 0-5 and 8-15: what mg_config.fuse = -1 selected before bit 16 (below) joined it */
     MG_FUSE_DEFAULT = MG_FUSE_RESNORM | MG_FUSE_PROLONG_SWEEP | MG_FUSE_RES_RESTRICT | MG_FUSE_NORM_SWEEP | MG_FUSE_MIXED_CORRECT | MG_FUSE_PAIRS |
                       MG_FUSE_COARSE_ZERO_SWEEP | MG_FUSE_LDS_TAIL | MG_FUSE_SWEEP_RESTRICT | MG_FUSE_ZERO_TRIPLE | MG_FUSE_PROLONG_PAIR |
                       MG_FUSE_TRIPLE_2D | MG_FUSE_PROLONG_PAIR_SLAB | MG_FUSE_CHEBY
 } mg_fuse_bits;
+/* (bit 16, 65536; fp64, 3-D, one rank, level 0 of 511- / 1023-wide whole grids, v0 = 3; with bits 10 and 12) the pass of bit 12 that makes the
+ * owed third post-smoothing sweep and the norm also makes the first TWO pre-smoothing sweeps of the next cycle, three sweeps in one pass
+ * (mgk_jacobi3_sumsq_mid_f64, include/mgk_sweep3.h), and the third one runs inside the restriction's pass (bit 10):
+ * (P + S1, S2)(S3, N + S1', S2')(S3' + R) = 25 + 24 + 26 = 75 B per fine unknown and cycle instead of 91.  The z-slab path keeps the 91-byte
+ * passes.  Same iterates and norms bit for bit.  The bit and MG_FUSE_AUTO stand beside the enum, whose enumerators and whose
+ * MG_FUSE_DEFAULT keep the values they have always had (ABI) */
+#define MG_FUSE_TRIPLE_MID 65536
+/* what mg_config.fuse = -1 selects: MG_FUSE_DEFAULT and bit 16 */
+#define MG_FUSE_AUTO (MG_FUSE_DEFAULT | MG_FUSE_TRIPLE_MID)
 
 /* options of the reference driver (src/poisson.c:51-59, poisson.in) + the PETSc options that
  * KSPSetFromOptions (src/solver.c:1476,1492,1509) would pick up for the smoother */
@@ -96,7 +105,7 @@ typedef struct mg_config {
                          * (below that a slab sweep is shorter than the latency of its halo exchange) */
     int fuse;           /* which fused passes a cycle may use: a mask of mg_fuse_bits (above).  Every bit exists so that tests can run the
                          * unfused path as the reference; which path runs is otherwise decided by what the solver sees (dimension, v0,
-                         * ranks).  -1 selects the default set, MG_FUSE_DEFAULT */
+                         * ranks).  -1 selects the default set, MG_FUSE_AUTO */
     int overlap;        /* nranks > 1: halo of sweep k on the comm stream while sweep k's interior runs; default on (-1) */
     int graph;          /* replay the launch-bound coarse levels as one captured HIP graph; default on (-1) */
     int pair_min_n;     /* levels with n >= pair_min_n run their sweeps two per pass (fuse bit 5); <=0: default 255 (3-D), 2047 (2-D) */
@@ -223,7 +232,8 @@ int  mg_solver_error_norms(mg_solver *s, double err[3]);
 /* per-kernel event timing of the fine-level smoother sweeps (bench.py roofline leg) */
 int  mg_solver_profile(mg_solver *s, int enable);
 int  mg_solver_profile_read(mg_solver *s, double *total_ms, int *launches);
-/* the same for one kind of launch: 0 = plain fine-level sweeps, 1 = two-sweeps-in-one-pass launches */
+/* the same for one kind of launch: 0 = plain fine-level sweeps, 1 = two-sweeps-in-one-pass launches (in the 75-byte cycle of fuse bit 16: the
+ * prolongation + two sweeps pass, the only one left on level 0), 2 = the three-sweep pass of fuse bit 16 */
 int  mg_solver_profile_read_kind(mg_solver *s, int kind, double *total_ms, int *launches);
 
 /* integer half of the reference (src/matbuild.c), implicit form */

@@ -369,7 +369,7 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         const int n0 = mg_grid_n(cfg->npts, 0);
         s->cfg.dist_min_n = n0 < 255 ? n0 : 255;
     }
-    if (s->cfg.fuse < 0) s->cfg.fuse = MG_FUSE_DEFAULT;
+    if (s->cfg.fuse < 0) s->cfg.fuse = MG_FUSE_AUTO;
     if (s->cfg.pair_min_n <= 0) s->cfg.pair_min_n = (cfg->dim == 3) ? 255 : 2047;   /* where a two-sweep pass beats two sweeps
                                                                                       * (255^3: 0.107 ms against 2 x 0.063) */
     /* line smoothers: the passes that bake point Jacobi in are off (bits 1, 3, 5, 8-15); the fused residual + norm (0) and residual +
@@ -1124,6 +1124,14 @@ static int pjp_ok(const mg_solver *s, int P) {
     }
     return mgk_prolong_jacobi2_ok_f64(&L->f[0].g, &s->L[1].f[0].g) && mgk_jacobi2_sumsq_ok_f64(&L->f[0].g);
 }
+/* fuse bit 16 (MG_FUSE_TRIPLE_MID; with bit 12 on one rank): the pass that makes the owed sweep and the norm also makes the first TWO
+ * pre-smoothing sweeps of the next cycle (mg_triple.c), whose third one the restriction's pass makes (bit 10): 25 + 24 + 26 = 75 B per fine
+ * unknown and cycle.  sweep_owed says that pjp_ok() held when the post-smoothing ran (v0 = 3, level 0 outside the coarse-level graph) */
+static int triple_mid_ok(const mg_solver *s) {
+    if (!(s->cfg.fuse & MG_FUSE_TRIPLE_MID) || !mg_triple_mid_pass || !mg_triple_mid_fits) return 0;
+    if (s->cfg.nranks != 1 || s->L[0].distributed || s->cfg.v[0] != 3 || s->lgraph == 1) return 0;
+    return srr_ok(s, 0, 0) && mg_triple_mid_fits(s);
+}
 static int finalize_iterate(mg_solver *s) {
     if (!s->iterate_behind) return 0;
     mg_level *L = &s->L[0];
@@ -1202,8 +1210,12 @@ static int prolong_smooth(mg_solver *s, int P, int l) {
     if (l == 0 && pjp_ok(s, P)) {
         /* the prolongation and the first TWO post-smoothing sweeps in one pass; the third one is made by the pass that evaluates the
          * norm (vcycle_once), which reads this field anyway */
-        CHK(mgk_prolong_jacobi2_f64(s->ctx, &F->g, &Cq->g, Lf->coef, Lf->dinv, s->cfg.scale, (const double *)F->b, (const double *)Cq->u,
-                                    (const double *)F->u, (double *)F->tmp, NULL));
+        /* (with fuse bit 16 this is the cycle's only launch of level 0 that makes two sweeps: timed as one, profile kind 1) */
+        void *t = triple_mid_ok(s) ? prof_begin_kind(s, 0, 1) : NULL;
+        int rc2 = mgk_prolong_jacobi2_f64(s->ctx, &F->g, &Cq->g, Lf->coef, Lf->dinv, s->cfg.scale, (const double *)F->b, (const double *)Cq->u,
+                                          (const double *)F->u, (double *)F->tmp, NULL);
+        prof_end(s, t);
+        CHK(rc2);
         swap_ptr(&F->u, &F->tmp);
         mgi_u_rewritten(F);
         s->sweep_owed = 1;
@@ -1561,6 +1573,17 @@ static int vcycle_once(mg_solver *s) {
 #undef J2M
             CHK(mgk_partials_finish(s->ctx, n1 + n2 + n3, &ss, NULL));
             s->sweep_owed = 0; s->iterate_behind = 1; s->spec_valid = 1;
+            goto norm_done;
+        }
+        if (s->sweep_owed && triple_mid_ok(s)) {
+            /* fuse bit 16: ... and the first TWO pre-smoothing sweeps of the next cycle (mg_triple.c): u stays one sweep behind the iterate,
+             * tmp is two sweeps ahead of it; smooth() adopts both and leaves the third to the restriction's pass (srr_ok).  Not timed as
+             * a two-sweep launch: profile kind 2 */
+            void *t = prof_begin_kind(s, 0, 2);
+            int rc2 = mg_triple_mid_pass(s, &ss);
+            prof_end(s, t);
+            CHK(rc2);
+            s->sweep_owed = 0; s->iterate_behind = 1; s->spec_valid = 2;
             goto norm_done;
         }
         if (s->sweep_owed) {

@@ -17,7 +17,7 @@
 /* y-line Jacobi: every pass that bakes POINT Jacobi into its kernel (bits 1, 3, 5, 8-15); the fused residual + norm and residual + restriction stay */
 #define MG_FUSE_POINT_JACOBI_PASSES (MG_FUSE_PROLONG_SWEEP | MG_FUSE_NORM_SWEEP | MG_FUSE_PAIRS | MG_FUSE_COARSE_ZERO_SWEEP | MG_FUSE_LDS_TAIL | \
                                      MG_FUSE_SWEEP_RESTRICT | MG_FUSE_ZERO_TRIPLE | MG_FUSE_PROLONG_PAIR | MG_FUSE_TRIPLE_2D | \
-                                     MG_FUSE_PROLONG_PAIR_SLAB | MG_FUSE_CHEBY)
+                                     MG_FUSE_PROLONG_PAIR_SLAB | MG_FUSE_CHEBY | MG_FUSE_TRIPLE_MID)
 /* row-dependent coefficients (-mesh 1/2; 2-D, fp64): the two passes that exist in 3-D alone and have no row-table form */
 #define MG_FUSE_NO_ROW_TABLE_FORM   (MG_FUSE_MIXED_CORRECT | MG_FUSE_RES_RESTRICT_SMALL)
 
@@ -141,6 +141,10 @@ extern int mg_line_tail(mg_solver *s) __attribute__((weak));      /* the levels 
  * references in the same way; mg_solver_create refuses the smoother in a build without it.  Every pass writes tmp and swaps u / tmp */
 extern int mg_rbgs_smooth(mg_solver *s, int l, int maxit) __attribute__((weak));   /* KSPSolve on level l: ceil(maxit / 2) passes */
 extern int mg_rbgs_prolong_smooth(mg_solver *s, int l, int maxit) __attribute__((weak));   /* u_l <- RB^maxit(u_l + P u_{l+1}), maxit >= 1: the first pass prolongs */
+/* the middle pass of the 75-byte 3-D fine level (fuse bit 16, MG_FUSE_TRIPLE_MID): mg_triple.c holds the only calls of mgk_jacobi3_sumsq_mid_f64 /
+ * mgk_jacobi3_mid_ok_f64 (include/mgk_sweep3.h), reached through WEAK references in the same way: a build without it runs the 91-byte passes */
+extern int mg_triple_mid_fits(const mg_solver *s) __attribute__((weak));          /* level 0 has a shape the pass is built for */
+extern int mg_triple_mid_pass(mg_solver *s, double *sumsq) __attribute__((weak)); /* level 0: tmp = J(J(J(u))), *sumsq = ||b - A J(u)||^2 */
 long mg_xline_stride(int n, int uniform);                                         /* row stride of the x table (mg_xline.c) */
 void mg_xline_factor(int n, int rows, const double *ctab, long gs, double *g);     /* the x table on the host (mg_xline.c) */
 

@@ -1,6 +1,7 @@
 // mgk_sweep3.hip -- three-sweep passes (2-D independent-wave forms; 3-D forms below).  Same build flags as every unit of libmgk.so
 // (-O3 -ffp-contract=off, gfx950 only); shares mgk_dev.hpp with them.
 #include "mgk_dev.hpp"
+#include "mgk_sweep3.h"
 #include <type_traits>
 
 // ------------------------------------------------------------------------------------------
@@ -614,15 +615,266 @@ static int jacobi3_3d(mgk_ctx *c, const mgk_geom *g, const double *coef, double 
     if constexpr (!NORM) return jacobi3_3d_launch<4, NORM>(c, a, g, coef, norm_parts, stream);      // (not built with a norm: it would spill)
     else return fail(MGK_EINVAL, "mgk_jacobi3_sumsq_f64: tile height not built");
 }
+// ------------------------------------------------------------------------------------------
+// THREE sweeps in one pass, 3-D, at TWO waves per SIMD: the eight waves of a 512-thread block are stacked in y.
+// A wave is 128 columns wide (lane l holds the column pair x0 = 2 (60 tx + l - 2): two halo lanes a side, x neighbours by DPP shifts, as
+// k_jacobi3_3d) and owns the SAME R rows at every stage: the block works on the 8 R rows yb-3 .. yb+8R-4 and the rows that are right shrink
+// by one a side per stage -- Y = 8 R - 6 rows are stored, the y-halo is paid once per block and not once per wave.  The y neighbours of a
+// wave's first and last row belong to the waves below and above: every wave deposits the first and the last row of the three planes that
+// are the CENTRE planes of the next step (u of plane t+3, first sweep of plane t+2, second sweep of plane t+1) in LDS at the end of a step, one
+// barrier, and the next step reads them: two buffers, one barrier per step.  The first wave's lower and the last wave's upper neighbour rows
+// are whatever LDS holds: they spoil exactly the rows that are not right anyway.  Per lane: u, first sweep, second sweep and b on R rows of
+// three planes each (12 R lane vectors; the plane that arrives from memory takes the slot of the plane that died: no copy), no AGPR, no
+// scratch.  At step t: first sweep of plane t+2, second sweep of plane t+1, third sweep of plane t (stored), as k_jacobi3_3d; a chunk
+// [z0, z1) starts four steps early.  EVERY wave of a block makes every step and reaches every barrier: the trip count is the block's, tiles
+// past the grid's edge work on clamped rows and store nothing, blocks past the last tile make no step.
+// NORM: 0 none; 1 || b - A u ||^2 of the input (the residual the first stage forms); 2 || b - A J(u) ||^2 (the second stage's): one partial
+// per block, summed in fixed order.
+// ------------------------------------------------------------------------------------------
+struct J3sArgs {
+    const double *u, *b;
+    double *out;
+    int nx, ny, nz;
+    long rs, ms;
+    int ntx, nty, ntz, zc, xcd;
+    double a0, a1, a2, a3, a4, a5, a6, dinv, scale;
+    double *partials;
+};
+#define J3S_WAVES 8
+#define J3S_ROWS 4
+template <int R, int NORM, bool EX>
+__global__ void __launch_bounds__(64 * J3S_WAVES) k_jacobi3s(const J3sArgs a) {
+    constexpr int NW = J3S_WAVES, Y = NW * R - 6;
+    constexpr unsigned XROW = 1024, XBUF = 3 * NW * 2 * XROW;   // a deposited row: 64 lanes x 16 B; a buffer: 3 fields x NW waves x 2 rows
+    using VT = V16<double>;
+    __shared__ __attribute__((aligned(16))) char xch[2 * XBUF];
+    const int lane = threadIdx.x & 63;
+    // wave-uniform values stay on the scalar unit
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int bid = blockIdx.x;
+    if (a.xcd) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+    const bool live = bid < a.ntx * a.nty * a.ntz;
+    const int tile = live ? bid : 0;
+    const int tx = tile % a.ntx, ty = (tile / a.ntx) % a.nty, tz = tile / (a.ntx * a.nty);
+    const int z0 = tz * a.zc, z1 = min(z0 + a.zc, a.nz);
+    const int t0 = z0 - 4, tend = live ? z1 : t0;
+    const int yb = ty * Y, yw = yb - 3 + w * R;
+    const int x0 = 2 * (tx * 60 + lane - 2);
+    const bool xin = (x0 >= 0 && x0 < a.nx);
+    const bool lastvec = (x0 + 2 > a.nx);
+    const bool store = (lane >= 2 && lane <= 61 && xin);
+    // lanes left / right of the grid read the zero padding of the row, as k_jacobi3_3d.  The lane's byte offset is kept unsigned (+32) beside
+    // a scalar base (-32): a 32-bit vector offset on a scalar address
+    const unsigned lo = (unsigned)(8 * min(x0, a.nx + 1) + 32);
+    const char *__restrict__ ub_ = reinterpret_cast<const char *>(a.u) - 32;
+    const char *__restrict__ bb_ = reinterpret_cast<const char *>(a.b) - 32;
+    char *__restrict__ ob_ = reinterpret_cast<char *>(a.out) - 32;
+    long uro[R], bro[R];                                      // (a stored row is inside the grid: its offset is b's)
+    unsigned long long rowm[R], rown[R];                      // all ones: the row is inside the grid / is one of the rows this block stores
+#pragma unroll
+    for (int q = 0; q < R; q++) {
+        const int y = yw + q;
+        uro[q] = 8 * (long)min(max(y, -1), a.ny) * a.rs;
+        bro[q] = 8 * (long)min(max(y, 0), a.ny - 1) * a.rs;
+        rowm[q] = (y >= 0 && y < a.ny) ? ~0ull : 0ull;
+        rown[q] = (y >= yb && y < yb + Y && y < a.ny) ? ~0ull : 0ull;
+    }
+    const unsigned long long Mx0 = xin ? ~0ull : 0ull, Mx1 = (xin && !lastvec) ? ~0ull : 0ull;
+    auto andm = [](double v, unsigned long long m) -> double { return __longlong_as_double((long long)((unsigned long long)__double_as_longlong(v) & m)); };
+    double nacc = 0.0;
+    // LDS: where this wave deposits its first (side 0) and last (side 1) row of field f, and where it finds its neighbours' rows
+    const unsigned xl = (unsigned)lane * 16u;
+    const unsigned xw = (unsigned)(w * 2) * XROW + xl;
+    const unsigned xs = (unsigned)(max(w - 1, 0) * 2 + 1) * XROW + xl;       // the last row of the wave below
+    const unsigned xn = (unsigned)(min(w + 1, NW - 1) * 2) * XROW + xl;      // the first row of the wave above
+    auto xput = [&](unsigned buf, int f, const VT &first, const VT &last) {
+        char *p = xch + buf + (unsigned)f * (NW * 2 * XROW) + xw;
+        *reinterpret_cast<VT *>(p) = first;
+        *reinterpret_cast<VT *>(p + XROW) = last;
+    };
+    auto xget = [&](unsigned buf, int f, VT &south, VT &north) {
+        const char *p = xch + buf + (unsigned)f * (NW * 2 * XROW);
+        south = *reinterpret_cast<const VT *>(p + xs);
+        north = *reinterpret_cast<const VT *>(p + xn);
+    };
+    auto ldu = [&](VT (&P)[R], int z) {
+        const char *pz = ub_ + 8 * (long)min(max(z, -1), a.nz) * a.ms;
+#pragma unroll
+        for (int q = 0; q < R; q++) P[q] = *reinterpret_cast<const VT *>(pz + uro[q] + (size_t)lo);
+    };
+    auto ldb = [&](VT (&P)[R], int z) {
+        const char *pz = bb_ + 8 * (long)min(max(z, 0), a.nz - 1) * a.ms;
+#pragma unroll
+        for (int q = 0; q < R; q++) P[q] = ldv_stream(reinterpret_cast<const double *>(pz + bro[q] + (size_t)lo), true);
+    };
+    // one sweep of the wave's R rows, term by term over the rows (the per-point expression and order of k_jacobi3_3d: 2 R independent sums).
+    // hs / hn: the rows below the first and above the last row of the centre plane.  zm: all ones if the plane is inside the grid;
+    // nm: all ones if the plane is one whose residual this block counts (read if `norm` only)
+    auto stage = [&](VT (&OUT)[R], const VT (&DN)[R], const VT &hs, const VT (&C)[R], const VT &hn, const VT (&UP)[R], const VT (&BB)[R],
+                     unsigned long long zm, auto maskrows, auto norm, unsigned long long nm) {
+        double s_[R][2];
+#pragma unroll
+        for (int q = 0; q < R; q++) { s_[q][0] = a.a0 * DN[q].v[0]; s_[q][1] = a.a0 * DN[q].v[1]; }
+#pragma unroll
+        for (int q = 0; q < R; q++) { const VT &sv = (q == 0) ? hs : C[q > 0 ? q - 1 : 0]; s_[q][0] = madd<EX>(s_[q][0], a.a1, sv.v[0]); s_[q][1] = madd<EX>(s_[q][1], a.a1, sv.v[1]); }
+#pragma unroll
+        for (int q = 0; q < R; q++) { s_[q][0] = madd<EX>(s_[q][0], a.a2, lane_up<true>(C[q].v[1])); s_[q][1] = madd<EX>(s_[q][1], a.a2, C[q].v[0]); }
+#pragma unroll
+        for (int q = 0; q < R; q++) { s_[q][0] = s_[q][0] + a.a3 * C[q].v[0]; s_[q][1] = s_[q][1] + a.a3 * C[q].v[1]; }
+#pragma unroll
+        for (int q = 0; q < R; q++) { s_[q][0] = madd<EX>(s_[q][0], a.a4, C[q].v[1]); s_[q][1] = madd<EX>(s_[q][1], a.a4, lane_dn<true>(C[q].v[0])); }
+#pragma unroll
+        for (int q = 0; q < R; q++) { const VT &nv = (q == R - 1) ? hn : C[q < R - 1 ? q + 1 : R - 1]; s_[q][0] = madd<EX>(s_[q][0], a.a5, nv.v[0]); s_[q][1] = madd<EX>(s_[q][1], a.a5, nv.v[1]); }
+#pragma unroll
+        for (int q = 0; q < R; q++) { s_[q][0] = madd<EX>(s_[q][0], a.a6, UP[q].v[0]); s_[q][1] = madd<EX>(s_[q][1], a.a6, UP[q].v[1]); }
+#pragma unroll
+        for (int q = 0; q < R; q++) {
+            const double r0 = BB[q].v[0] - s_[q][0], r1 = BB[q].v[1] - s_[q][1];
+            const double zz0 = r0 * a.dinv, zz1 = r1 * a.dinv;
+            const double v0 = C[q].v[0] + a.scale * zz0, v1 = C[q].v[1] + a.scale * zz1;
+            const unsigned long long mu = decltype(maskrows)::value ? (rowm[q] & zm) : ~0ull;
+            OUT[q].v[0] = andm(v0, Mx0 & mu); OUT[q].v[1] = andm(v1, Mx1 & mu);
+            if constexpr (decltype(norm)::value) {
+                const unsigned long long mn = rown[q] & nm;
+                const double n0 = andm(r0, mn), n1 = andm(r1, Mx1 & mn);      // (lanes that store nothing: discarded at the end)
+                nacc += n0 * n0; nacc += n1 * n1;
+            }
+        }
+    };
+    using yes = std::true_type; using no = std::false_type;
+    const VT Z = v16_zero<double>();
+    // rings of three planes, indexed by the step's phase (t - t0) mod 3: the marching loop is unrolled by three and every index is a constant
+    VT U[3][R];                                               // u:            planes t+1, t+2, t+3 in the slots PH, PH+1, PH+2 (mod 3)
+    VT P[3][R];                                               // first sweep:  planes t, t+1, (new) t+2
+    VT Q[3][R];                                               // second sweep: planes t-1, t, (new) t+1
+    VT B[3][R];                                               // b:            planes t, t+1, t+2
+    ldu(U[0], t0 + 1); ldu(U[1], t0 + 2); ldu(U[2], t0 + 3);
+    ldb(B[2], t0 + 2);
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int q = 0; q < R; q++) { P[k][q] = Z; Q[k][q] = Z; if (k < 2) B[k][q] = Z; }
+    xput(0, 0, U[1][0], U[1][R - 1]);                         // the centre plane of the first step's first sweep
+    __syncthreads();
+    auto step = [&](auto phc, int t) {
+        constexpr int PH = decltype(phc)::value, S0 = PH % 3, S1 = (PH + 1) % 3, S2 = (PH + 2) % 3;
+        const unsigned rb = (unsigned)((t - t0) & 1) * XBUF, wb = XBUF - rb;
+        const unsigned long long z2m = (t + 2 >= 0 && t + 2 < a.nz) ? ~0ull : 0ull, z1m = (t + 1 >= 0 && t + 1 < a.nz) ? ~0ull : 0ull;
+        const unsigned long long z2own = (t + 2 >= z0 && t + 2 < z1) ? ~0ull : 0ull, z1own = (t + 1 >= z0 && t + 1 < z1) ? ~0ull : 0ull;
+        VT hs, hn;
+        // first sweep of plane t+2 into the slot the dead plane t-1 held
+        xget(rb, 0, hs, hn);
+        stage(P[S2], U[S0], hs, U[S1], hn, U[S2], B[S2], z2m, yes{}, std::integral_constant<bool, NORM == 1>{}, z2own);
+        ldu(U[S0], t + 4);                                    // plane t+4 takes the place of plane t+1 (dead since the first sweep)
+        if (t >= z0 - 2) {
+            // second sweep of plane t+1
+            xget(rb, 1, hs, hn);
+            stage(Q[S2], P[S0], hs, P[S1], hn, P[S2], B[S1], z1m, yes{}, std::integral_constant<bool, NORM == 2>{}, z1own);
+            if (t >= z0) {
+                // third sweep of plane t
+                VT O[R];
+                xget(rb, 2, hs, hn);
+                stage(O, Q[S0], hs, Q[S1], hn, Q[S2], B[S0], ~0ull, no{}, no{}, 0ull);
+                char *pz = ob_ + 8 * (long)t * a.ms;
+#pragma unroll
+                for (int q = 0; q < R; q++)
+                    if (store && rown[q]) stv_stream(reinterpret_cast<double *>(pz + bro[q] + (size_t)lo), O[q]);
+            }
+        }
+        ldb(B[S0], t + 3);                                    // b of plane t+3 takes the place of b of plane t
+        // the first and last rows of the next step's centre planes
+        xput(wb, 0, U[S2][0], U[S2][R - 1]);
+        xput(wb, 1, P[S2][0], P[S2][R - 1]);
+        xput(wb, 2, Q[S2][0], Q[S2][R - 1]);
+        __syncthreads();
+    };
+    for (int t = t0; t < tend; t += 3) {
+        step(std::integral_constant<int, 0>{}, t);
+        if (t + 1 < tend) step(std::integral_constant<int, 1>{}, t + 1);
+        if (t + 2 < tend) step(std::integral_constant<int, 2>{}, t + 2);
+    }
+    if (NORM) {
+        const double sb = block_sum(store ? nacc : 0.0, reinterpret_cast<double *>(xch));
+        if (threadIdx.x == 0) a.partials[blockIdx.x] = sb;
+    }
+}
+static bool jacobi3s_shape_ok(const mgk_geom *g) { return g && g->dim == 3 && (g->nx + 1 == 512 || g->nx + 1 == 1024); }
+// which form the three-sweep entry points take: the stacked one where it is asked for by name (other shapes are then refused) and, unless the
+// knob names the independent-wave form or one of its variants, on the shapes it is built for -- it is the faster one there (1023^3: 5.60
+// against 7.27 ms, with the norm of the input 5.92 against 7.3; 511^3: 0.68 against 0.91; profiles/triple_mid/README.md)
+static int jacobi3s_takes(const mgk_geom *g) {
+    if (g_variant == MGK_TUNE_J3_3D_STACKED || g_variant == MGK_TUNE_J3_3D_STACKED_DISPATCH) return 1;
+    if (g_variant == MGK_TUNE_J3_3D_WAVES || g_variant == MGK_TUNE_J3_3D_TY2 || g_variant == MGK_TUNE_J3_3D_TY3 || g_variant == MGK_TUNE_J3_3D_ROWWISE ||
+        g_variant == MGK_TUNE_DISPATCH_ORDER) return 0;
+    return jacobi3s_shape_ok(g) ? 1 : 0;
+}
+template <int NORM>
+static int jacobi3s(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale, const double *b, const double *u, double *unew,
+                    void *stream, int *norm_parts, const char *who) {
+    static thread_local char msg[160];
+    if (!c || !g || g->dim != 3 || !coef || !b || !u || !unew || u == unew || b == unew) {
+        snprintf(msg, sizeof(msg), "%s: bad arguments (3-D; unew must not be u or b)", who);
+        return fail(MGK_EINVAL, msg);
+    }
+    if (!jacobi3s_shape_ok(g)) {
+        snprintf(msg, sizeof(msg), "%s: the stacked three-sweep pass is built for whole 3-D grids with rows of 512 or 1024 (nx = 511, 1023)", who);
+        return fail(MGK_EINVAL, msg);
+    }
+    // rows per wave: 4 (244-249 registers per lane, none in scratch); with the norm of the input 3: the first stage forms that norm while
+    // every ring is live, and the 4-row form would spill 19 registers to scratch
+    constexpr int R = (NORM == 1) ? 3 : J3S_ROWS, Y = J3S_WAVES * R - 6;
+    J3sArgs a; memset(&a, 0, sizeof(a));
+    a.u = u + g->org; a.b = b + g->org; a.out = unew + g->org;
+    a.nx = g->nx; a.ny = g->ny; a.nz = g->nz; a.rs = g->pitch; a.ms = g->plane;
+    set_coef7(a, coef);
+    a.dinv = dinv; a.scale = scale;
+    a.ntx = ((g->nx + 1) / 2 + 59) / 60;
+    a.nty = (g->ny + Y - 1) / Y;
+    // one block per CU (two waves per SIMD): cut z so that the blocks make whole rounds of the 256 CUs, as nearly as what a chunk costs beside
+    // its planes allows -- four recomputed planes and the fill of the pipeline, 12 planes' worth together.  Measured at 1023^3 (360 tiles;
+    // profiles/triple_mid/README.md): 2 chunks (2.8 rounds) 5.45 ms, 7 (9.8) 5.53, 4 (5.6) 5.64, 3 (4.2) 5.89, 1 (1.4) 6.39 -- the order of this cost
+    const long per = (long)a.ntx * a.nty;
+    long best = 1; double bestc = 0.0;
+    for (long n = 1; n <= 16 && g->nz / n >= 8; n++) {
+        const double cost = (double)((per * n + 255) / 256) * (double)((g->nz + n - 1) / n + 12);
+        if (n == 1 || cost < bestc) { best = n; bestc = cost; }
+    }
+    const Chunks ch = cut_chunks_n(c, g->nz, best, {/*min*/ 8, /*zchunk below*/ true, /*even*/ false, /*clamp*/ true, /*hint*/ 0, 0});
+    a.zc = ch.len; a.ntz = (int)ch.count;
+    unsigned nblk = (unsigned)(per * a.ntz);
+    a.xcd = (g_variant != MGK_TUNE_J3_3D_STACKED_DISPATCH && nblk >= 64) ? 1 : 0;
+    if (a.xcd) nblk = (nblk + 7u) & ~7u;
+    if (NORM) {
+        if (!norm_parts || (long)nblk > c->max_partials) { snprintf(msg, sizeof(msg), "%s: more blocks than partial slots", who); return fail(MGK_EINVAL, msg); }
+        a.partials = c->partials;
+        *norm_parts = (int)nblk;
+    }
+    if (exact_fma7(coef)) hipLaunchKernelGGL((k_jacobi3s<R, NORM, true>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
+    else hipLaunchKernelGGL((k_jacobi3s<R, NORM, false>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 extern "C" int mgk_jacobi3_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                                const double *b, const double *u, double *unew, void *stream) {
+    if (jacobi3s_takes(g)) return jacobi3s<0>(c, g, coef, dinv, scale, b, u, unew, stream, nullptr, "mgk_jacobi3_f64");
     return jacobi3_3d<false>(c, g, coef, dinv, scale, b, u, unew, stream, nullptr);
+}
+extern "C" int mgk_jacobi3_mid_ok_f64(const mgk_geom *g) { return jacobi3s_shape_ok(g) ? 1 : 0; }
+// Three sweeps and sumsq = || b - A J(u) ||^2, the residual of the FIRST sweep's output (which is not stored): unew = J(J(J(u))).
+extern "C" int mgk_jacobi3_sumsq_mid_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
+                                         const double *b, const double *u, double *unew, double *sumsq_host, void *stream) {
+    if (!sumsq_host) return fail(MGK_EINVAL, "mgk_jacobi3_sumsq_mid_f64: bad arguments");
+    int nparts = 0;
+    int rc = jacobi3s<2>(c, g, coef, dinv, scale, b, u, unew, stream, &nparts, "mgk_jacobi3_sumsq_mid_f64");
+    if (rc) return rc;
+    return finish_to_host(c, nparts, 1, S(c, stream), sumsq_host);
 }
 extern "C" int mgk_jacobi3_sumsq_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                                      const double *b, const double *u, double *unew, double *sumsq_host, void *stream) {
     if (!sumsq_host) return fail(MGK_EINVAL, "mgk_jacobi3_sumsq_f64: bad arguments");
     int nparts = 0;
-    int rc = jacobi3_3d<true>(c, g, coef, dinv, scale, b, u, unew, stream, &nparts);
+    int rc = jacobi3s_takes(g) ? jacobi3s<1>(c, g, coef, dinv, scale, b, u, unew, stream, &nparts, "mgk_jacobi3_sumsq_f64")
+                               : jacobi3_3d<true>(c, g, coef, dinv, scale, b, u, unew, stream, &nparts);
     if (rc) return rc;
     return finish_to_host(c, nparts, 1, S(c, stream), sumsq_host);
 }

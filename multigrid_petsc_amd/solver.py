@@ -27,7 +27,7 @@ class MgError(RuntimeError):
 
 class Fuse(enum.IntFlag):
     """The bits of Solver(fuse=...), mg_config.fuse: mg_fuse_bits of include/mgsolve.h, which says what each pass is.  The values are ABI
-    (plain ints are taken everywhere); value 64 is unassigned, accepted and ignored.  fuse=-1 selects DEFAULT."""
+    (plain ints are taken everywhere); value 64 is unassigned, accepted and ignored.  fuse=-1 selects FUSE_AUTO (below): DEFAULT and bit 16."""
     RESNORM = 1
     PROLONG_SWEEP = 2
     RES_RESTRICT = 4
@@ -45,6 +45,11 @@ class Fuse(enum.IntFlag):
     CHEBY = 32768
     DEFAULT = (RESNORM | PROLONG_SWEEP | RES_RESTRICT | NORM_SWEEP | MIXED_CORRECT | PAIRS | COARSE_ZERO_SWEEP | LDS_TAIL | SWEEP_RESTRICT |
                ZERO_TRIPLE | PROLONG_PAIR | TRIPLE_2D | PROLONG_PAIR_SLAB | CHEBY)
+
+
+# MG_FUSE_TRIPLE_MID / MG_FUSE_AUTO of include/mgsolve.h: bit 16 stands beside the enum there and here (the enumerators mirror the C enum one to one)
+FUSE_TRIPLE_MID = 65536
+FUSE_AUTO = int(Fuse.DEFAULT) | FUSE_TRIPLE_MID
 
 
 _KSP = {"richardson": 0, "chebyshev": 1}
@@ -275,7 +280,7 @@ class Solver:
 
     def profile_read(self, kind=0):
         """(total ms, launches) of the fine-level launches timed since profile(True): kind 0 plain sweeps,
-        kind 1 two-sweeps-in-one-pass launches"""
+        kind 1 two-sweeps-in-one-pass launches, kind 2 the three-sweep pass of fuse bit 16"""
         ms, n = C.c_double(), C.c_int()
         self._chk(self.L.mg_solver_profile_read_kind(self.h, kind, C.byref(ms), C.byref(n)))
         return ms.value, n.value

@@ -43,5 +43,7 @@ for _ in range(2):
     m._chk(L.mgk_jacobi2_sumsq_mid_f64(m.ctx, C.byref(g), coef, dinv, 6.0 / 7.0, b, u, out, C.byref(ss), None))
     m._chk(L.mgk_residual_restrict_jz_f64(m.ctx, C.byref(g), C.byref(gc), coef, b, u, bc, uc, dinv, 6.0 / 7.0, None))
     m._chk(L.mgk_jacobi3_f64(m.ctx, C.byref(g), coef, dinv, 6.0 / 7.0, b, u, out, None))
+    # the stacked three-sweep pass of the 75-byte fine level (k_jacobi3s, mid-norm form)
+    m._chk(L.mgk_jacobi3_sumsq_mid_f64(m.ctx, C.byref(g), coef, dinv, 6.0 / 7.0, b, u, out, C.byref(ss), None))
 m.sync()
 m.close()
