@@ -730,7 +730,9 @@ enum mgk_tune {
                                           off-diagonal coefficients are +-2^e, e >= 0, and the exact-FMA form would be taken (same results) */
     MGK_TUNE_J3_3D_WAVES       = 66,   /* jacobi3_3d: the independent-wave form k_jacobi3_3d, one wave per SIMD, on rows of 512 / 1024 too */
     MGK_TUNE_J3_3D_STACKED     = 67,   /* jacobi3_3d: the stacked form k_jacobi3s, two waves per SIMD (rows of 512 / 1024, where it is the default; other shapes refused) */
-    MGK_TUNE_J3_3D_STACKED_DISPATCH = 68   /* jacobi3_3d, jacobi3_sumsq_mid: the stacked form with its tiles in dispatch order */
+    MGK_TUNE_J3_3D_STACKED_DISPATCH = 68,  /* jacobi3_3d, jacobi3_sumsq_mid, prolong_jacobi3: the stacked form with its tiles in dispatch order */
+    MGK_TUNE_NO_PROLONG_TRIPLE = 69    /* the prolongation + three-sweep pass (include/mgk_sweep3.h) is not offered: its _ok_ query answers 0 and the callers
+                                          that ask it keep their two passes (the A/B switch of one build) */
 };
 
 /* tuning knobs (profiling only), per calling thread: <=0 keeps the built-in choice.  They are GLOBAL to that thread, not per kernel -- set

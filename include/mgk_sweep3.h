@@ -19,6 +19,16 @@ int  mgk_jacobi3_mid_ok_f64(const mgk_geom *g);
 int  mgk_jacobi3_sumsq_mid_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef, double dinv, double scale,
                                const double *b, const double *u, double *unew, double *sumsq_host, void *stream);
 
+/* 1 if mgk_prolong_jacobi3_f64 is built for the pair of geometries: gf a whole 3-D grid with rows of 512 or 1024 points and gf = 2 gc + 1 in
+ * every direction.  0 under MGK_TUNE_NO_PROLONG_TRIPLE (the entry point itself stays callable) */
+int  mgk_prolong_jacobi3_ok_f64(const mgk_geom *gf, const mgk_geom *gc);
+/* unew = J(J(J(u + P uc))): the prolongation, its correction and three post-smoothing sweeps in one pass of 25 B per fine unknown (u, b and
+ * uc / 8 read, unew written once).  Bit-identical to mgk_prolong_jacobi_f64 followed by two mgk_jacobi_f64.  unew must not be u, b or uc;
+ * u, b and uc are not modified.  Other shapes: MGK_EINVAL with a message.  Knobs: the chunk length in z, MGK_TUNE_J3_3D_STACKED_DISPATCH,
+ * MGK_TUNE_NO_EXACT_FMA. */
+int  mgk_prolong_jacobi3_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
+                             const double *b, const double *uc, const double *u, double *unew, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,7 +80,10 @@ typedef enum mg_fuse_bits {
  * owed third post-smoothing sweep and the norm also makes the first TWO pre-smoothing sweeps of the next cycle, three sweeps in one pass
  * (mgk_jacobi3_sumsq_mid_f64, include/mgk_sweep3.h), and the third one runs inside the restriction's pass (bit 10):
  * (P + S1, S2)(S3, N + S1', S2')(S3' + R) = 25 + 24 + 26 = 75 B per fine unknown and cycle instead of 91.  The z-slab path keeps the 91-byte
- * passes.  Same iterates and norms bit for bit.  The bit and MG_FUSE_AUTO stand beside the enum, whose enumerators and whose
+ * passes.  Same iterates and norms bit for bit.  The same bit (3-D, fp64, one rank, Richardson + point Jacobi, v0 >= 3): where the post-smoothing
+ * of a 511- / 1023-wide level outside the coarse-level graph is not made by bit 12 -- level 1 of a 1025^3 solve, level 0 in the last cycle of a
+ * call -- the prolongation, its correction and three sweeps run as one pass (mgk_prolong_jacobi3_f64): 25 instead of 49 B per unknown of that
+ * level.  The bit and MG_FUSE_AUTO stand beside the enum, whose enumerators and whose
  * MG_FUSE_DEFAULT keep the values they have always had (ABI) */
 #define MG_FUSE_TRIPLE_MID 65536
 /* what mg_config.fuse = -1 selects: MG_FUSE_DEFAULT and bit 16 */
@@ -218,6 +221,8 @@ int  mg_solver_num_levels(const mg_solver *s);
 /* the first level that runs inside a tail kernel (fuse bit 9, or line_tail with a line smoother): it and every coarser level are one launch
  * per cycle, their fields in LDS; 0: none */
 int  mg_solver_tail_level(const mg_solver *s);
+/* launches of the prolongation + three-sweep pass (fuse bit 16) on a level since the solver was created */
+int  mg_solver_prolong_triple_launches(const mg_solver *s, int level);
 int  mg_solver_level_n(const mg_solver *s, int level);              /* unknowns per side */
 int  mg_solver_level_local_planes(const mg_solver *s, int level, int *z0);
 long mg_solver_local_unknowns(const mg_solver *s);

@@ -1132,6 +1132,16 @@ static int triple_mid_ok(const mg_solver *s) {
     if (s->cfg.nranks != 1 || s->L[0].distributed || s->cfg.v[0] != 3 || s->lgraph == 1) return 0;
     return srr_ok(s, 0, 0) && mg_triple_mid_fits(s);
 }
+/* the same bit in the generic branch of prolong_smooth(): the prolongation, its correction and the first THREE post-smoothing sweeps of level l in
+ * one pass (mg_triple.c).  The level then swaps u / tmp once where the two passes swapped twice, so the pass stays off the levels whose
+ * pointers the coarse-level graph has recorded: the levels inside it and the one that feeds it */
+static int prolong_triple_ok(const mg_solver *s, int P, int l) {
+    if (!(s->cfg.fuse & MG_FUSE_TRIPLE_MID) || !mg_triple_prolong_pass || !mg_triple_prolong_fits) return 0;
+    if (P != 0 || s->cfg.dim != 3 || s->cfg.mesh || s->cfg.ksp_type != MG_KSP_RICHARDSON || s->cfg.pc_type != MG_PC_JACOBI || s->cfg.v[0] < 3) return 0;
+    if (s->cfg.nranks != 1 || s->L[l].distributed || s->L[l + 1].distributed) return 0;
+    if (s->lgraph && l >= s->lgraph - 1) return 0;
+    return mg_triple_prolong_fits(s, l);
+}
 static int finalize_iterate(mg_solver *s) {
     if (!s->iterate_behind) return 0;
     mg_level *L = &s->L[0];
@@ -1220,6 +1230,14 @@ static int prolong_smooth(mg_solver *s, int P, int l) {
         mgi_u_rewritten(F);
         s->sweep_owed = 1;
         return 0;
+    }
+    if (prolong_triple_ok(s, P, l)) {
+        /* 3-D, rows of 512 / 1024: the prolongation, the correction and the first THREE post-smoothing sweeps in one pass (25 instead of
+         * 25 + 24 B per unknown); one swap */
+        CHK(mg_triple_prolong_pass(s, l));
+        swap_ptr(&F->u, &F->tmp);
+        mgi_u_rewritten(F);
+        return v0 > 3 ? smooth(s, P, l, v0 - 3, 0) : 0;
     }
     mgk_geom gc = Cq->g;
     const void *ucoarse = Cq->u;
@@ -1804,6 +1822,7 @@ const double *mg_solver_rnorm(const mg_solver *s) { return s->rnorm; }
 double mg_solver_solve_seconds(const mg_solver *s) { return s->solve_seconds; }
 int mg_solver_num_levels(const mg_solver *s) { return s->levels; }
 int mg_solver_tail_level(const mg_solver *s) { return s ? s->ltail : 0; }
+int mg_solver_prolong_triple_launches(const mg_solver *s, int l) { return (s && l >= 0 && l < s->levels) ? s->prolong_triple_launches[l] : 0; }
 int mg_solver_level_n(const mg_solver *s, int l) { return (l >= 0 && l < s->levels) ? s->L[l].n : -1; }
 int mg_solver_level_local_planes(const mg_solver *s, int l, int *z0) {
     if (l < 0 || l >= s->levels) return -1;

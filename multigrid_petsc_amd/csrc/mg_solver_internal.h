@@ -92,6 +92,7 @@ struct mg_solver {
     void *coarse_graph[2];  /* one recording per precision */
     void *graph_u[2], *graph_tmp[2];   /* u / tmp of the level that feeds the recording, as the recorded kernels know them */
     int graph_rerecorded;   /* recordings thrown away because those pointers had changed (0 in every default configuration) */
+    int prolong_triple_launches[MG_MAX_LEVELS];   /* launches of the prolongation + three-sweep pass per level since the solver was created (mg_triple.c) */
     /* profiling */
     int prof_on, prof_n;
     void *timers[MG_MAX_TIMERS];
@@ -145,6 +146,10 @@ extern int mg_rbgs_prolong_smooth(mg_solver *s, int l, int maxit) __attribute__(
  * mgk_jacobi3_mid_ok_f64 (include/mgk_sweep3.h), reached through WEAK references in the same way: a build without it runs the 91-byte passes */
 extern int mg_triple_mid_fits(const mg_solver *s) __attribute__((weak));          /* level 0 has a shape the pass is built for */
 extern int mg_triple_mid_pass(mg_solver *s, double *sumsq) __attribute__((weak)); /* level 0: tmp = J(J(J(u))), *sumsq = ||b - A J(u)||^2 */
+/* the same bit, the generic post-smoothing of a 511- / 1023-wide level outside the coarse-level graph: the prolongation, its correction and three
+ * sweeps in one pass (mgk_prolong_jacobi3_f64, named by mg_triple.c alone) instead of prolongation + sweep and a two-sweep pass */
+extern int mg_triple_prolong_fits(const mg_solver *s, int l) __attribute__((weak));   /* levels l, l + 1 have shapes the pass is built for */
+extern int mg_triple_prolong_pass(mg_solver *s, int l) __attribute__((weak));         /* level l: tmp = J(J(J(u + P u_{l+1}))); counts the launch */
 long mg_xline_stride(int n, int uniform);                                         /* row stride of the x table (mg_xline.c) */
 void mg_xline_factor(int n, int rows, const double *ctab, long gs, double *g);     /* the x table on the host (mg_xline.c) */
 

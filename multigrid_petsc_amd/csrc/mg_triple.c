@@ -8,7 +8,7 @@
  *
  * u stays one sweep behind the iterate the norm belongs to (it is never stored), tmp is two sweeps ahead of it.  mg_solver.c decides WHERE the
  * pass runs (vcycle_once) and keeps the flags; this file is the only host code that calls the kernel, and mg_solver.c refers to it weakly
- * (mg_solver_internal.h): a build without it runs the 91-byte passes.
+ * (mg_solver_internal.h): a build without it runs the 91-byte passes.  Below it, the same bit's prolongation + three-sweep pass.
  */
 #include "mg_solver_internal.h"
 #include "mgk_sweep3.h"
@@ -26,5 +26,25 @@ int mg_triple_mid_pass(mg_solver *s, double *sumsq) {
     mg_fset *F = &L->f[0];
     CHK(mgk_jacobi3_sumsq_mid_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u, (double *)F->tmp,
                                   sumsq, NULL));
+    return 0;
+}
+
+/* The prolongation form of the same kernel: where the post-smoothing of a level runs through the generic branch of
+ * prolong_smooth() -- level 1 of a 1025^3 solve in every cycle, level 0 in the last cycle of a call -- (P + S1)(S2, S3) = 25 + 24 B becomes
+ * (P + S1, S2, S3) = 25 B per unknown of that level.  The level swaps u / tmp once instead of twice: mg_solver.c takes the pass only on
+ * levels whose pointers no recording holds. */
+int mg_triple_prolong_fits(const mg_solver *s, int l) {
+    if (s->cfg.dim != 3 || l < 0 || l + 1 >= s->levels) return 0;
+    const mg_level *Lf = &s->L[l], *Lc = &s->L[l + 1];
+    return !Lf->distributed && !Lc->distributed && mgk_prolong_jacobi3_ok_f64(&Lf->f[0].g, &Lc->f[0].g);
+}
+
+/* tmp = J(J(J(u + P u_{l+1}))) on level l.  Not timed as a profile kind (kinds 0 - 2 describe other launches); counted per level instead */
+int mg_triple_prolong_pass(mg_solver *s, int l) {
+    mg_level *L = &s->L[l];
+    mg_fset *F = &L->f[0], *Cq = &s->L[l + 1].f[0];
+    CHK(mgk_prolong_jacobi3_f64(s->ctx, &F->g, &Cq->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)Cq->u,
+                                (const double *)F->u, (double *)F->tmp, NULL));
+    s->prolong_triple_launches[l]++;
     return 0;
 }

@@ -640,14 +640,31 @@ struct J3sArgs {
     double a0, a1, a2, a3, a4, a5, a6, dinv, scale;
     double *partials;
 };
+// PRO: the coarse field of the prolongation form (geometry of the coarse level: ghost ring -1 .. nc, row pitch, plane stride)
+struct J3spArgs : J3sArgs {
+    const double *uc;
+    int nxc, nyc, nzc;
+    long crs, cms;
+};
 #define J3S_WAVES 8
 #define J3S_ROWS 4
-template <int R, int NORM, bool EX>
-__global__ void __launch_bounds__(64 * J3S_WAVES) k_jacobi3s(const J3sArgs a) {
+// PRO: unew = J(J(J(u + P uc))), the prolongation, its correction and three post-smoothing sweeps in one pass of
+// 25 B per unknown.  Every u plane that arrives is corrected to u + P uc at the top of the step that first reads it (plane t+3 in step t;
+// the arithmetic of correct() in k_pj2r3: parent planes, rows, columns ascending, weights wk * (wi * wj)) and masked to zero outside the
+// grid, so the rows deposited for the neighbouring waves are the corrected ones.  Coarse values: every wave keeps the NCR = 3 coarse rows
+// that are the parents of its R rows, at the coarse columns of its 64 pairs, in a ring of three coarse planes in LDS (slot k mod 3; column
+// c of the wave's 64 at [c + 1], [0] a zero pad: the left parent of lane 0's even column, which no stored column depends on).  A new
+// coarse plane is due every second step: plane (t + 4) / 2 is requested at the top of an EVEN step t (global parity: a chunk may start at
+// any z), stored into its slot before the barrier that ends the step and first read in step t + 1.  Coarse indices are clamped into the
+// ghost ring -1 .. nc: what a clamped index reads lands on positions the masks clear.
+template <int R, int NORM, bool EX, bool PRO = false>
+__global__ void __launch_bounds__(64 * J3S_WAVES) k_jacobi3s(const typename std::conditional<PRO, J3spArgs, J3sArgs>::type a) {
     constexpr int NW = J3S_WAVES, Y = NW * R - 6;
     constexpr unsigned XROW = 1024, XBUF = 3 * NW * 2 * XROW;   // a deposited row: 64 lanes x 16 B; a buffer: 3 fields x NW waves x 2 rows
+    constexpr int NCR = 3, LC = 66;                             // PRO: coarse rows per wave and plane; columns (64 + the pad, even)
     using VT = V16<double>;
     __shared__ __attribute__((aligned(16))) char xch[2 * XBUF];
+    __shared__ __attribute__((aligned(16))) double cbf[PRO ? 3 * NW * NCR * LC : 1];
     const int lane = threadIdx.x & 63;
     // wave-uniform values stay on the scalar unit
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -741,6 +758,59 @@ __global__ void __launch_bounds__(64 * J3S_WAVES) k_jacobi3s(const J3sArgs a) {
             }
         }
     };
+    // PRO: the wave's rows yw .. yw+R-1 have the parent rows jb .. jb+2, jb = floor((yw - 1) / 2); with yw = 2 jb + 1 + ev row yw + q has the
+    // first parent jb + ((ev + q) >> 1) and, if ev + q is odd (an even fine row), the next one as well (R even: yw is odd, ev = 0)
+    const int ev = (R & 1) ? ((yw & 1) ^ 1) : 0;
+    const double *ucl = nullptr;                              // the lane's coarse column (clamped into the ghost ring)
+    long cro[NCR] = {0, 0, 0};
+    double *cbw = cbf + (unsigned)w * (NCR * LC) + (unsigned)lane;        // + slot * NW * NCR * LC + row * LC: [0] the left parent, [1] the own one
+    if constexpr (PRO) {
+        const int jb = (yw - 1) >> 1;
+        ucl = a.uc + min(max(tx * 60 + lane - 2, -1), a.nxc);
+#pragma unroll
+        for (int j = 0; j < NCR; j++) cro[j] = (long)min(max(jb + j, -1), a.nyc) * a.crs;
+    }
+    auto cslot = [](int k) -> unsigned { return (unsigned)(((k % 3) + 3) % 3) * (NW * NCR * LC); };
+    auto ldc = [&](double (&cl)[NCR], int k) {
+        if constexpr (PRO) {
+            const double *pk = ucl + (long)min(max(k, -1), a.nzc) * a.cms;
+#pragma unroll
+            for (int j = 0; j < NCR; j++) cl[j] = pk[cro[j]];
+        }
+    };
+    auto stc = [&](const double (&cl)[NCR], int k) {
+        double *p = cbw + cslot(k) + 1;
+#pragma unroll
+        for (int j = 0; j < NCR; j++) p[j * LC] = cl[j];
+    };
+    // u + P uc on the wave's R rows of plane z; outside the grid (ghost ring, padding, rows and planes beyond) the result is zero
+    auto correct = [&](VT (&P_)[R], int z) {
+        const bool two = ((z & 1) == 0);
+        const int kl = (z - 1) >> 1;
+        const double *cA = cbw + cslot(kl), *cB = cbw + cslot(kl + 1);
+        const double wk = two ? 0.5 : 1.0;
+        const unsigned long long zm = (z >= 0 && z < a.nz) ? ~0ull : 0ull;
+#pragma unroll
+        for (int q = 0; q < R; q++) {
+            const bool tworows = (((ev + q) & 1) != 0);
+            const int j0 = (ev + q) >> 1;
+            const double wi = tworows ? 0.5 : 1.0;
+            const double wh = wk * (wi * 0.5), w1 = wk * (wi * 1.0);
+            double s0 = 0.0, s1 = 0.0;
+            {   // parent plane kl (always)
+                const double c0 = cA[j0 * LC], c1 = cA[j0 * LC + 1];
+                s0 += wh * c0; s0 += wh * c1; s1 += w1 * c1;
+                if (tworows) { const double d0 = cA[(j0 + 1) * LC], d1 = cA[(j0 + 1) * LC + 1]; s0 += wh * d0; s0 += wh * d1; s1 += w1 * d1; }
+            }
+            if (two) {   // block-uniform: an even plane has a second parent plane
+                const double c0 = cB[j0 * LC], c1 = cB[j0 * LC + 1];
+                s0 += wh * c0; s0 += wh * c1; s1 += w1 * c1;
+                if (tworows) { const double d0 = cB[(j0 + 1) * LC], d1 = cB[(j0 + 1) * LC + 1]; s0 += wh * d0; s0 += wh * d1; s1 += w1 * d1; }
+            }
+            const unsigned long long mu = rowm[q] & zm;
+            P_[q].v[0] = andm(P_[q].v[0] + s0, Mx0 & mu); P_[q].v[1] = andm(P_[q].v[1] + s1, Mx1 & mu);
+        }
+    };
     using yes = std::true_type; using no = std::false_type;
     const VT Z = v16_zero<double>();
     // rings of three planes, indexed by the step's phase (t - t0) mod 3: the marching loop is unrolled by three and every index is a constant
@@ -754,11 +824,27 @@ __global__ void __launch_bounds__(64 * J3S_WAVES) k_jacobi3s(const J3sArgs a) {
     for (int k = 0; k < 3; k++)
 #pragma unroll
         for (int q = 0; q < R; q++) { P[k][q] = Z; Q[k][q] = Z; if (k < 2) B[k][q] = Z; }
+    if constexpr (PRO) {
+        // the parents of the planes t0+1 .. t0+3 are the coarse planes m .. m+2, m = floor(t0 / 2); plane t0+3 is corrected by the first step
+        const int m = t0 >> 1;
+        double c0[NCR], c1[NCR], c2[NCR];
+        ldc(c0, m); ldc(c1, m + 1); ldc(c2, m + 2);
+        for (int i = threadIdx.x; i < 3 * NW * NCR; i += 64 * NW) cbf[i * LC] = 0.0;      // the pads
+        stc(c0, m); stc(c1, m + 1); stc(c2, m + 2);
+        __syncthreads();
+        correct(U[0], t0 + 1); correct(U[1], t0 + 2);
+    }
     xput(0, 0, U[1][0], U[1][R - 1]);                         // the centre plane of the first step's first sweep
     __syncthreads();
     auto step = [&](auto phc, int t) {
         constexpr int PH = decltype(phc)::value, S0 = PH % 3, S1 = (PH + 1) % 3, S2 = (PH + 2) % 3;
         const unsigned rb = (unsigned)((t - t0) & 1) * XBUF, wb = XBUF - rb;
+        double cnew[NCR];
+        const bool newc = PRO && ((t & 1) == 0);                // block-uniform
+        if constexpr (PRO) {
+            if (newc) ldc(cnew, (t + 4) >> 1);
+            correct(U[S2], t + 3);                              // the plane requested in the last step (the prologue, for the first one)
+        }
         const unsigned long long z2m = (t + 2 >= 0 && t + 2 < a.nz) ? ~0ull : 0ull, z1m = (t + 1 >= 0 && t + 1 < a.nz) ? ~0ull : 0ull;
         const unsigned long long z2own = (t + 2 >= z0 && t + 2 < z1) ? ~0ull : 0ull, z1own = (t + 1 >= z0 && t + 1 < z1) ? ~0ull : 0ull;
         VT hs, hn;
@@ -786,6 +872,7 @@ __global__ void __launch_bounds__(64 * J3S_WAVES) k_jacobi3s(const J3sArgs a) {
         xput(wb, 0, U[S2][0], U[S2][R - 1]);
         xput(wb, 1, P[S2][0], P[S2][R - 1]);
         xput(wb, 2, Q[S2][0], Q[S2][R - 1]);
+        if constexpr (PRO) { if (newc) stc(cnew, (t + 4) >> 1); }
         __syncthreads();
     };
     for (int t = t0; t < tend; t += 3) {
@@ -808,12 +895,18 @@ static int jacobi3s_takes(const mgk_geom *g) {
         g_variant == MGK_TUNE_DISPATCH_ORDER) return 0;
     return jacobi3s_shape_ok(g) ? 1 : 0;
 }
-template <int NORM>
+// PRO: the prolongation form, unew = J(J(J(u + P uc))) with uc on the coarse grid gc (g = 2 gc + 1 in every direction); no norm
+template <int NORM, bool PRO = false>
 static int jacobi3s(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale, const double *b, const double *u, double *unew,
-                    void *stream, int *norm_parts, const char *who) {
-    static thread_local char msg[160];
+                    void *stream, int *norm_parts, const char *who, const mgk_geom *gc = nullptr, const double *uc = nullptr) {
+    static_assert(!PRO || NORM == 0, "the prolongation form forms no norm");
+    static thread_local char msg[200];
     if (!c || !g || g->dim != 3 || !coef || !b || !u || !unew || u == unew || b == unew) {
         snprintf(msg, sizeof(msg), "%s: bad arguments (3-D; unew must not be u or b)", who);
+        return fail(MGK_EINVAL, msg);
+    }
+    if (PRO && (!gc || !uc || uc == unew || gc->dim != 3 || g->nx != 2 * gc->nx + 1 || g->ny != 2 * gc->ny + 1 || g->nz != 2 * gc->nz + 1)) {
+        snprintf(msg, sizeof(msg), "%s: bad arguments (the fine grid must be 2 n + 1 points of the coarse one in every direction; unew must not be uc)", who);
         return fail(MGK_EINVAL, msg);
     }
     if (!jacobi3s_shape_ok(g)) {
@@ -823,7 +916,10 @@ static int jacobi3s(mgk_ctx *c, const mgk_geom *g, const double *coef, double di
     // rows per wave: 4 (244-249 registers per lane, none in scratch); with the norm of the input 3: the first stage forms that norm while
     // every ring is live, and the 4-row form would spill 19 registers to scratch
     constexpr int R = (NORM == 1) ? 3 : J3S_ROWS, Y = J3S_WAVES * R - 6;
-    J3sArgs a; memset(&a, 0, sizeof(a));
+    typename std::conditional<PRO, J3spArgs, J3sArgs>::type a; memset(&a, 0, sizeof(a));
+    if constexpr (PRO) {
+        a.uc = uc + gc->org; a.nxc = gc->nx; a.nyc = gc->ny; a.nzc = gc->nz; a.crs = gc->pitch; a.cms = gc->plane;
+    }
     a.u = u + g->org; a.b = b + g->org; a.out = unew + g->org;
     a.nx = g->nx; a.ny = g->ny; a.nz = g->nz; a.rs = g->pitch; a.ms = g->plane;
     set_coef7(a, coef);
@@ -849,10 +945,21 @@ static int jacobi3s(mgk_ctx *c, const mgk_geom *g, const double *coef, double di
         a.partials = c->partials;
         *norm_parts = (int)nblk;
     }
-    if (exact_fma7(coef)) hipLaunchKernelGGL((k_jacobi3s<R, NORM, true>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
-    else hipLaunchKernelGGL((k_jacobi3s<R, NORM, false>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
+    if (exact_fma7(coef)) hipLaunchKernelGGL((k_jacobi3s<R, NORM, true, PRO>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
+    else hipLaunchKernelGGL((k_jacobi3s<R, NORM, false, PRO>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
     HIPCHK(hipGetLastError());
     return 0;
+}
+// Prolongation, correction and three post-smoothing sweeps in one pass: unew = J(J(J(u + P uc))), the stacked pass's prolongation form
+// (k_jacobi3s<.., PRO>).  Bit-identical to mgk_prolong_jacobi_f64 followed by two mgk_jacobi_f64.  MGK_TUNE_NO_PROLONG_TRIPLE: not offered
+extern "C" int mgk_prolong_jacobi3_ok_f64(const mgk_geom *gf, const mgk_geom *gc) {
+    if (g_variant == MGK_TUNE_NO_PROLONG_TRIPLE) return 0;
+    if (!jacobi3s_shape_ok(gf) || !gc || gc->dim != 3) return 0;
+    return (gf->nx == 2 * gc->nx + 1 && gf->ny == 2 * gc->ny + 1 && gf->nz == 2 * gc->nz + 1) ? 1 : 0;
+}
+extern "C" int mgk_prolong_jacobi3_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
+                                       const double *b, const double *uc, const double *u, double *unew, void *stream) {
+    return jacobi3s<0, true>(c, gf, coef, dinv, scale, b, u, unew, stream, nullptr, "mgk_prolong_jacobi3_f64", gc, uc);
 }
 extern "C" int mgk_jacobi3_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                                const double *b, const double *u, double *unew, void *stream) {

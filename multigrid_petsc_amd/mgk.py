@@ -56,6 +56,7 @@ class Tune(enum.IntEnum):
     J3_3D_WAVES = 66
     J3_3D_STACKED = 67
     J3_3D_STACKED_DISPATCH = 68
+    NO_PROLONG_TRIPLE = 69
 
 
 @contextlib.contextmanager
@@ -186,6 +187,8 @@ def _sigs(L):
         "mgk_jacobi3_sumsq_f64": (i, [vp, G, c_dp, d, d, vp, vp, vp, C.POINTER(d), vp]),
         "mgk_jacobi3_sumsq_mid_f64": (i, [vp, G, c_dp, d, d, vp, vp, vp, C.POINTER(d), vp]),
         "mgk_jacobi3_mid_ok_f64": (i, [G]),
+        "mgk_prolong_jacobi3_ok_f64": (i, [G, G]),
+        "mgk_prolong_jacobi3_f64": (i, [vp, G, G, c_dp, d, d, vp, vp, vp, vp, vp]),
         "mgk_jacobi3_2d_f64": (i, [vp, G, c_dp, d, d, vp, vp, vp, vp, vp, vp]),
         "mgk_jacobi3_2d_sumsq_f64": (i, [vp, G, c_dp, d, d, vp, vp, vp, vp, vp, C.POINTER(d), vp]),
         "mgk_jacobi3_2d_zero_f64": (i, [vp, G, c_dp, d, d, vp, vp, vp, vp, vp]),

@@ -86,6 +86,8 @@ def _lib():
     L.mg_solver_num_levels.argtypes = [vp]
     L.mg_solver_tail_level.restype = i
     L.mg_solver_tail_level.argtypes = [vp]
+    L.mg_solver_prolong_triple_launches.restype = i
+    L.mg_solver_prolong_triple_launches.argtypes = [vp, i]
     L.mg_solver_level_n.restype = i
     L.mg_solver_level_n.argtypes = [vp, i]
     L.mg_solver_level_local_planes.restype = i
@@ -256,6 +258,10 @@ class Solver:
     def tail_level(self):
         """the first level that runs inside a tail kernel (fuse bit 9; line_tail for the line smoothers); 0: none"""
         return self.L.mg_solver_tail_level(self.h)
+
+    def prolong_triple_launches(self, l):
+        """launches of the prolongation + three-sweep pass (fuse bit 16, mgk_prolong_jacobi3_f64) on level l since the solver was created"""
+        return self.L.mg_solver_prolong_triple_launches(self.h, l)
 
     def level_n(self, l):
         return self.L.mg_solver_level_n(self.h, l)

@@ -45,5 +45,7 @@ for _ in range(2):
     m._chk(L.mgk_jacobi3_f64(m.ctx, C.byref(g), coef, dinv, 6.0 / 7.0, b, u, out, None))
     # the stacked three-sweep pass of the 75-byte fine level (k_jacobi3s, mid-norm form)
     m._chk(L.mgk_jacobi3_sumsq_mid_f64(m.ctx, C.byref(g), coef, dinv, 6.0 / 7.0, b, u, out, C.byref(ss), None))
+    # its prolongation form: prolongation + three sweeps in one pass (k_jacobi3s<.., PRO>)
+    m._chk(L.mgk_prolong_jacobi3_f64(m.ctx, C.byref(g), C.byref(gc), coef, dinv, 6.0 / 7.0, b, uc, u, out, None))
 m.sync()
 m.close()
