@@ -281,6 +281,13 @@ int  mgk_tail_max_n(int dim);
 /* profiling aid: the tail kernels this thread launches deposit (s_memrealtime [100 MHz], s_memtime [shader clock]) pairs at each of their
  * barriers into dev[0 .. 255] and the number of pairs into dev[256] (257 long longs of DEVICE memory; NULL switches it off) */
 void mgk_debug_tail_stamps(long long *dev);
+/* test aids for the reduction scratch of a context: every entry point that returns a sum of squares, a dot product or an error norm deposits
+ * per-block / per-wave partials there and a finishing kernel adds up the slots it was told of.
+ * mgk_debug_partials: the device address of the scratch, *allocated = the doubles allocated (3 rows of 16384 slots); fill and read it with
+ * mgk_h2d / mgk_d2h.  mgk_debug_set_max_partials: lowers the number of slots per row that every launcher may use to n (1 .. 16384; 0 restores
+ * 16384; MGK_EINVAL otherwise).  The allocation does not change, and the several-row reductions lay their rows n slots apart. */
+double *mgk_debug_partials(mgk_ctx *ctx, long *allocated);
+int  mgk_debug_set_max_partials(mgk_ctx *ctx, int n);
 
 /* ---- K6: VecNorm(NORM_2) (src/solver.c:1512,1518,1546): returns sum of squares of the interior ---- */
 int  mgk_sumsq_f64(mgk_ctx *ctx, const mgk_geom *g, const double *x, double *sumsq_host, void *stream);

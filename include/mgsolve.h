@@ -218,6 +218,8 @@ const double *mg_solver_rnorm(const mg_solver *s);
 double mg_solver_solve_seconds(const mg_solver *s);       /* "Solver walltime" window (src/solver.c:1526,1553) */
 
 int  mg_solver_num_levels(const mg_solver *s);
+/* test aid: the kernel context (mgk_ctx *, include/mgk.h) this solver launches on, for mgk_debug_partials / mgk_sync; NULL without a solver */
+void *mg_solver_debug_kernel_ctx(mg_solver *s);
 /* the first level that runs inside a tail kernel (fuse bit 9, or line_tail with a line smoother): it and every coarser level are one launch
  * per cycle, their fields in LDS; 0: none */
 int  mg_solver_tail_level(const mg_solver *s);

@@ -1821,6 +1821,7 @@ double mg_solver_bnorm(const mg_solver *s) { return s->bnorm; }
 const double *mg_solver_rnorm(const mg_solver *s) { return s->rnorm; }
 double mg_solver_solve_seconds(const mg_solver *s) { return s->solve_seconds; }
 int mg_solver_num_levels(const mg_solver *s) { return s->levels; }
+void *mg_solver_debug_kernel_ctx(mg_solver *s) { return s ? (void *)s->ctx : NULL; }
 int mg_solver_tail_level(const mg_solver *s) { return s ? s->ltail : 0; }
 int mg_solver_prolong_triple_launches(const mg_solver *s, int l) { return (s && l >= 0 && l < s->levels) ? s->prolong_triple_launches[l] : 0; }
 int mg_solver_level_n(const mg_solver *s, int l) { return (l >= 0 && l < s->levels) ? s->L[l].n : -1; }

@@ -19,7 +19,7 @@ struct mgk_ctx {
     double *partials;      // reduction scratch (device)
     double *result_dev;    // MGK_RESULT_SLOTS doubles (device)
     double *result_host;   // MGK_RESULT_SLOTS doubles (pinned host): the landing area of reduced values
-    int max_partials;
+    int max_partials;      // slots a reduction may use per row of the scratch: MGK_PARTIAL_SLOTS, or less under mgk_debug_set_max_partials
     hipEvent_t ev[32];     // ring of dependency events for mgk_stream_wait (no create/destroy on the hot path)
     int ev_next;
     double *defer_slot;    // non-null: the next single-value reductions deposit here (device) instead of syncing to the host
@@ -52,6 +52,7 @@ struct mgk_preload_unit {
 };
 #define MGK_PRELOAD_UNIT(...) static const mgk_preload_unit mgk_preload_this_unit(reinterpret_cast<const void *>(__VA_ARGS__));
 #include "mgk_launch.hpp"        // the launch rules of the host side (they read the context and the knobs above)
+#define MGK_PARTIAL_SLOTS 16384  // the scratch holds 3 rows of this many doubles; c->max_partials never exceeds it
 #define MGK_RESULT_SLOTS 64      // >= MGK_KRYLOV_MAX + 1: the dots of an Arnoldi step and the norm that follows them
 
 // ------------------------------------------------------------------------------------------

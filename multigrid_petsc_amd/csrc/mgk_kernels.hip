@@ -64,8 +64,8 @@ static int ctx_build(mgk_ctx *c) {
             HIPCHK(hipStreamCreateWithFlags(&c->comm, hipStreamNonBlocking));
     }
     c->chunk_planes = 0;
-    c->max_partials = 16384;
-    HIPCHK(hipMalloc(&c->partials, sizeof(double) * 3 * c->max_partials));
+    c->max_partials = MGK_PARTIAL_SLOTS;
+    HIPCHK(hipMalloc(&c->partials, sizeof(double) * 3 * MGK_PARTIAL_SLOTS));
     HIPCHK(hipMalloc(&c->result_dev, sizeof(double) * MGK_RESULT_SLOTS));
     HIPCHK(hipHostMalloc(&c->result_host, sizeof(double) * MGK_RESULT_SLOTS, hipHostMallocDefault));
     for (int q = 0; q < 32; q++) HIPCHK(hipEventCreateWithFlags(&c->ev[q], hipEventDisableTiming));
@@ -830,7 +830,7 @@ static int launch_st(mgk_ctx *c, StArgs<T> &a, int nrows, hipStream_t s, int *nb
     if (REDUCE && nblk > c->max_partials) {
         // fewer, longer chunks so that the partial buffer suffices
         ntz = c->max_partials / tiles;
-        if (ntz < 1) return fail(MGK_EINVAL, "stencil launch: partial buffer too small");
+        if (ntz < 1) return fail(MGK_EINVAL, "stencil launch: more tiles than partial slots");
         zc = (int)((nmr + ntz - 1) / ntz);
         a.zc = zc;
         ntz = (nmr + zc - 1) / zc;
@@ -978,6 +978,18 @@ extern "C" int mgk_apply_f64(mgk_ctx *c, const mgk_geom *g, const double *coef,
 extern "C" int mgk_defer_result(mgk_ctx *c, double *slot_dev) {
     if (!c) return fail(MGK_EINVAL, "mgk_defer_result: null context");
     c->defer_slot = slot_dev;
+    return 0;
+}
+// test aids: the reduction scratch itself (device address, doubles allocated), and a lower slot cap for every launcher.  The allocation
+// stays: under a lowered cap a launcher that overran its slots would land in allocated memory, where a test that filled it can see it
+extern "C" double *mgk_debug_partials(mgk_ctx *c, long *allocated) {
+    if (!c) return nullptr;
+    if (allocated) *allocated = 3L * MGK_PARTIAL_SLOTS;
+    return c->partials;
+}
+extern "C" int mgk_debug_set_max_partials(mgk_ctx *c, int n) {
+    if (!c || n < 0 || n > MGK_PARTIAL_SLOTS) return fail(MGK_EINVAL, "mgk_debug_set_max_partials: the cap is 1 .. 16384 partial slots (0 restores 16384)");
+    c->max_partials = n ? n : MGK_PARTIAL_SLOTS;
     return 0;
 }
 int finish_to_host(mgk_ctx *c, int nparts, int nslots, hipStream_t s, double *host_out) {
@@ -2238,8 +2250,9 @@ static int jacobi2(mgk_ctx *c, const mgk_geom *g, const double *coef, double din
     if (norm_parts) {
         // with the residual norm of the input field: the register form on full-row shapes only
         constexpr int WRn = 64 * VX;
-        if (sizeof(T) != 8 || (g->nx + 1) % WRn != 0 || (g->ny + 1) % 4 != 0 || part_off < 0 || (long)nblk > c->max_partials - part_off)
+        if (sizeof(T) != 8 || (g->nx + 1) % WRn != 0 || (g->ny + 1) % 4 != 0 || part_off < 0)
             return fail(MGK_EINVAL, "mgk_jacobi2_sumsq: built for fp64 full-row shapes (n = 127, 255, 511, 1023)");
+        if ((long)nblk > c->max_partials - part_off) return fail(MGK_EINVAL, "mgk_jacobi2_sumsq: more blocks than partial slots");
         a.partials = c->partials + part_off;
         if constexpr (sizeof(T) == 8) {                                 // (the norm forms are built for fp64 only)
             const bool exn = exact_fma7(coef);
@@ -3228,6 +3241,7 @@ extern "C" int mgk_sumsq_f64(mgk_ctx *c, const mgk_geom *g, const double *x, dou
     RowArgs a = row_args(g);
     dim3 grid, block;
     row_grid(a, a.npairs, grid, block, 1024);
+    if ((long)grid.x * grid.y > c->max_partials) return fail(MGK_EINVAL, "mgk_sumsq_f64: more blocks than partial slots");
     hipLaunchKernelGGL(k_sumsq, grid, block, 0, S(c, stream), a, x + g->org, c->partials);
     HIPCHK(hipGetLastError());
     return finish_to_host(c, (int)(grid.x * grid.y), 1, S(c, stream), sumsq_host);
@@ -3250,6 +3264,7 @@ extern "C" int mgk_error_sums_f64(mgk_ctx *c, const mgk_geom *g, const double *u
     RowArgs a = row_args(g);
     dim3 grid, block;
     row_grid(a, a.npairs, grid, block, 1024);
+    if ((long)grid.x * grid.y > c->max_partials) return fail(MGK_EINVAL, "mgk_error_sums_f64: more blocks than partial slots (three rows of them)");
     hipStream_t s = S(c, stream);
     hipLaunchKernelGGL(k_error_sums, grid, block, 0, s, a, u + g->org, sx, sy, g->dim == 3 ? sz : nullptr, c->partials, c->max_partials);
     HIPCHK(hipGetLastError());
@@ -4558,7 +4573,7 @@ static int launch_jrow(mgk_ctx *c, const mgk_geom *g, const StArgs<T> &a, int zb
     long nblk = (long)q.nty * ch.count;
     if (NORM && nblk > max_partials) {                       // fewer, longer chunks so that the partial buffer suffices
         const long ntz = max_partials / q.nty;
-        if (ntz < 1) return fail(MGK_EINVAL, "row sweep: partial buffer too small");
+        if (ntz < 1) return fail(MGK_EINVAL, "row sweep: more tiles than partial slots");
         zc = (int)((nzr + ntz - 1) / ntz);
         nblk = (long)q.nty * ((nzr + zc - 1) / zc);
     }

@@ -224,6 +224,7 @@ extern "C" int mgk_multi_axpy_sumsq_f64(mgk_ctx *c, const mgk_geom *g, int k, co
     for (int i = 0; i < k; i++) if (v[i] == w) return fail(MGK_EINVAL, "mgk_multi_axpy_sumsq_f64: w is one of the operands");
     dim3 grid, block;
     kry_grid(a, grid, block);
+    if ((long)grid.x * grid.y > c->max_partials) return fail(MGK_EINVAL, "mgk_multi_axpy_sumsq_f64: more blocks than partial slots");
     hipStream_t s = S(c, stream);
 #define CALL(KB) hipLaunchKernelGGL(k_multi_axpy_sumsq<KB>, grid, block, 0, s, a, h_dev, w + g->org, c->partials)
     KRY_DISPATCH(k, CALL);

@@ -289,7 +289,10 @@ static int jacobi3_2d(mgk_ctx *c, const mgk_geom *g, const mgk_geom *gc, const d
     long waves = (long)a.ntx * ((g->ny + yc - 1) / yc);
     if (NORM && ((waves + 3) / 4 + 7) * 4 > c->max_partials) {    // one partial per wave: longer chunks where that would overflow the slots
         if (ycs) { ycs = 0; }
-        const long maxch = c->max_partials / a.ntx - 1;
+        // the slots are handed out by whole blocks of four waves, by whole groups of eight blocks in the XCD tile order (which a refitted
+        // launch takes only if forced or from 4095 columns on): refit to what is left of the cap after that rounding
+        const long slots = (g_variant == MGK_TUNE_XCD_ORDER || g->nx >= 4095) ? (c->max_partials & ~31) : (c->max_partials & ~3);
+        const long maxch = slots / a.ntx;
         if (maxch < 1) return fail(MGK_EINVAL, "mgk_jacobi3_2d_sumsq_f64: more waves than partial slots");
         yc = (int)((g->ny + maxch - 1) / maxch);
         waves = (long)a.ntx * ((g->ny + yc - 1) / yc);

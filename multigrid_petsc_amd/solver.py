@@ -84,6 +84,8 @@ def _lib():
     L.mg_solver_solve_seconds.argtypes = [vp]
     L.mg_solver_num_levels.restype = i
     L.mg_solver_num_levels.argtypes = [vp]
+    L.mg_solver_debug_kernel_ctx.restype = vp
+    L.mg_solver_debug_kernel_ctx.argtypes = [vp]
     L.mg_solver_tail_level.restype = i
     L.mg_solver_tail_level.argtypes = [vp]
     L.mg_solver_prolong_triple_launches.restype = i
@@ -258,6 +260,11 @@ class Solver:
     def tail_level(self):
         """the first level that runs inside a tail kernel (fuse bit 9; line_tail for the line smoothers); 0: none"""
         return self.L.mg_solver_tail_level(self.h)
+
+    @property
+    def kernel_ctx(self):
+        """the kernel context (mgk_ctx *) the solver launches on, as a c_void_p: a test aid (mgk_debug_partials)"""
+        return C.c_void_p(self.L.mg_solver_debug_kernel_ctx(self.h))
 
     def prolong_triple_launches(self, l):
         """launches of the prolongation + three-sweep pass (fuse bit 16, mgk_prolong_jacobi3_f64) on level l since the solver was created"""

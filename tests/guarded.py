@@ -21,6 +21,12 @@ watched for WHERE a call stores, the half of the kernel ABI's contract that a co
    An output whose content the body has fetched is poisoned again before the next library call that is handed it, so a body that reuses one
    output over its variants without clearing it gives every call a poisoned one.  The proxy counts, per watched entry point, the calls that
    were handed a still-poisoned output (`poisoned_calls`).
+ * scratch: the context's reduction scratch (mgk_debug_partials: 3 x 16384 doubles that every sum of squares, dot product and error norm
+   deposits its per-block / per-wave partials in, never cleared, shared by all of them) is filled with the same NaN before every call of an
+   entry point of REDUCERS, the whole allocation: a slot that the finishing kernel adds up and the launch did not write turns the returned sum
+   into NaN, where without the fill it holds the right value from the tuning variant before, or zero.  The range forms gather the partials
+   of several calls before one mgk_partials_finish: only a call with part_off == 0 opens such a group and is preceded by the fill.  The
+   proxy counts the calls so treated per entry point (`scratch_poisoned_calls`).
  * L is a recording wrapper: it forwards every attribute and logs the name of each function called (`calls`).
 
 Not asserted: out-of-bounds READS, and what the padding of an input may hold.  Neither is in the contract.
@@ -80,6 +86,19 @@ def kij(g, off):
     return (k, r // g.pitch - 1, r % g.pitch - xoff)
 
 
+# the entry points whose launcher hands the context's reduction scratch to a kernel (tests/test_reduction_scratch_cpu.py derives the same set from
+# csrc/*.hip); value: the index of the call's part_off argument, None where the call reduces its own partials
+REDUCERS = {
+    "mgk_residual_sumsq_f64": None, "mgk_jacobi_sumsq_f64": None, "mgk_jacobi_sumsq_store_f64": None, "mgk_jacobi_sumsq_range_f64": 10,
+    "mgk_jacobi2_sumsq_f64": None, "mgk_jacobi2_sumsq_mid_f64": None, "mgk_jacobi2_sumsq_slab_f64": 14, "mgk_jacobi2_sumsq_mid_slab_f64": 14,
+    "mgk_jacobi2_2d_sumsq_f64": None, "mgk_jacobi2_2d_sumsq_rowcoef_f64": None, "mgk_sumsq_f64": None, "mgk_error_sums_f64": None,
+    "mgk_flat_dot": None, "mgk_residual_f64_to_f32": None, "mgk_residual_f64_to_f32_jz": None, "mgk_correct_residual_f64_f32": None,
+    "mgk_correct_residual_f64_f32_jz": None, "mgk_jacobi_sumsq_rowcoef_f64": None, "mgk_residual_sumsq_rowcoef_f64": None,
+    "mgk_jacobi3_2d_sumsq_f64": None, "mgk_jacobi3_2d_sumsq_store_f64": None, "mgk_cheby3_2d_sumsq_f64": None, "mgk_jacobi3_sumsq_f64": None,
+    "mgk_jacobi3_sumsq_mid_f64": None, "mgk_multi_dot_f64": None, "mgk_multi_axpy_sumsq_f64": None,
+}
+
+
 class _Buf:
     def __init__(self, base, nbytes, geom=None, dtype=None, init=None, output=False):
         self.base, self.nbytes, self.geom, self.dtype, self.init = base, nbytes, geom, dtype, init
@@ -129,6 +148,8 @@ class Guarded:
         self.watch = frozenset()            # entry points whose calls are looked at: did one get a still-poisoned field?
         self.poisoned_calls = {}            # name -> calls of it that were handed at least one still-poisoned output field
         self.repoisoned = 0                 # whole-field mgk_memset0 calls of the body after which the poison was put back
+        self.scratch_poisoned_calls = {}    # name -> calls of a REDUCERS entry before which the whole reduction scratch was filled with the poison
+        self._scratch = None                # (device address, doubles) of the context's reduction scratch
         self.ctx, self.symbols = mgk.ctx, mgk.symbols
         self.live = {}                      # handed-out address -> _Buf
         self.frame_checks = self.guard_checks = self.whole_downloads = 0    # whole_downloads: allocations handed back to the body in full
@@ -143,6 +164,10 @@ class Guarded:
 
     def sync(self):
         self.inner.sync()
+
+    def last_error(self):
+        """the message of the calling thread's last refused call"""
+        return self.L.mgk_last_error().decode()
 
     # -- what the body does through L --
     _WRITERS = {"mgk_memset0": 1, "mgk_h2d": 1, "mgk_h2d_async": 1, "mgk_d2d": 1}          # name -> index of the destination pointer
@@ -160,7 +185,33 @@ class Guarded:
         buf.poisoned, buf.taken = True, False
         self.repoisoned += 1
 
+    # -- the reduction scratch --
+    def scratch(self):
+        """(device address, doubles allocated) of the context's reduction scratch"""
+        if self._scratch is None:
+            n = C.c_long()
+            p = self.inner.L.mgk_debug_partials(self.ctx, C.byref(n))
+            assert p and n.value > 0, "mgk_debug_partials"
+            self._scratch = (p if isinstance(p, int) else p.value, n.value)
+        return self._scratch
+
+    def poison_scratch(self):
+        addr, n = self.scratch()
+        self.inner.sync()
+        self._h2d(addr, np.full(n, poison_value(np.float64)))
+
+    def read_scratch(self):
+        addr, n = self.scratch()
+        self.inner.sync()
+        return self.inner.download(C.c_void_p(addr), n)
+
     def _before(self, name, args):
+        if name in REDUCERS and self.poison:
+            off = REDUCERS[name]
+            off = 0 if off is None else (args[off].value if hasattr(args[off], "value") else int(args[off]))
+            if off == 0:                                # (a later range of a group must find the partials of the ranges before it)
+                self.poison_scratch()
+                self.scratch_poisoned_calls[name] = self.scratch_poisoned_calls.get(name, 0) + 1
         if name not in self._WRITERS and self.poison:
             for b in map(self._known, args):            # an output whose result the body has taken already: the next kernel must not find it there
                 if b is not None and b.output and b.taken:
@@ -383,4 +434,4 @@ EXEMPT = {
     "mgk_rbgs_2d_f64": _RBGS, "mgk_prolong_rbgs_2d_f64": _RBGS,
 }
 
-__all__ = ["EXEMPT", "Guarded", "HostMgk", "MissingStandIn", "MgkError", "SENTINEL", "GUARD_DOUBLES", "interior", "layout", "kij", "is_poison", "poison_value"]
+__all__ = ["EXEMPT", "REDUCERS", "Guarded", "HostMgk", "MissingStandIn", "MgkError", "SENTINEL", "GUARD_DOUBLES", "interior", "layout", "kij", "is_poison", "poison_value"]

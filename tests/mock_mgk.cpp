@@ -24,7 +24,8 @@ struct mgk_ctx {
     double *defer;
     bool capturing;
     std::vector<std::function<void()>> rec;
-    std::vector<double> partials;
+    std::vector<double> partials;      // 3 x 16384, as the context's reduction scratch (mgk_debug_partials)
+    int max_partials;                  // the slot cap (mgk_debug_set_max_partials)
 };
 struct mock_graph { std::vector<std::function<void()>> ops; };
 static thread_local char g_err[256] = "ok";
@@ -57,7 +58,7 @@ int mgk_geom_init_f32(mgk_geom *g, int dim, int nx, int ny, int nz) {
 int mgk_ctx_create(mgk_ctx **out, int device) {
     if (!out) return fail(MGK_EINVAL, "mgk_ctx_create");
     mgk_ctx *c = new mgk_ctx();
-    c->device = device; c->defer = nullptr; c->capturing = false; c->partials.assign(16384, 0.0);
+    c->device = device; c->defer = nullptr; c->capturing = false; c->partials.assign(3 * 16384, 0.0); c->max_partials = 16384;
     *out = c;
     return 0;
 }
@@ -106,6 +107,16 @@ int mgk_defer_result(mgk_ctx *c, double *slot) { c->defer = slot; return 0; }
 void mgk_set_tuning(int, int) {}
 int mgk_tail_max_n(int dim) { return dim == 3 ? 15 : 63; }
 void mgk_debug_tail_stamps(long long *) {}
+double *mgk_debug_partials(mgk_ctx *c, long *allocated) {
+    if (!c) return nullptr;
+    if (allocated) *allocated = (long)c->partials.size();
+    return c->partials.data();
+}
+int mgk_debug_set_max_partials(mgk_ctx *c, int n) {
+    if (!c || n < 0 || n > 16384) return fail(MGK_EINVAL, "mgk_debug_set_max_partials: the cap is 1 .. 16384 partial slots");
+    c->max_partials = n ? n : 16384;
+    return 0;
+}
 }   // extern "C"
 
 // ---------------------------------------------------------------------------------------------
@@ -355,7 +366,7 @@ int mgk_residual_sumsq_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, co
 }
 int mgk_jacobi_sumsq_range_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale, const double *b, const double *u, double *o,
                                int z0, int z1, int part_off, int *nparts, void *) {
-    if (!c || !g || !coef || !b || !u || !o || u == o || !nparts || part_off < 0 || part_off >= (int)c->partials.size()) return fail(MGK_EINVAL, "mgk_jacobi_sumsq_range_f64");
+    if (!c || !g || !coef || !b || !u || !o || u == o || !nparts || part_off < 0 || part_off >= c->max_partials) return fail(MGK_EINVAL, "mgk_jacobi_sumsq_range_f64");
     CHKRANGE(g, z0, z1, "mgk_jacobi_sumsq_range_f64: range");
     std::vector<double> r(g->total, 0.0);
     st_op<double>(M_RESIDUAL, *g, coef, 1, 1, 0, 0, 0, b, u, (const double *)nullptr, r.data(), z0, z1);
@@ -365,7 +376,7 @@ int mgk_jacobi_sumsq_range_f64(mgk_ctx *c, const mgk_geom *g, const double *coef
     return 0;
 }
 int mgk_partials_finish(mgk_ctx *c, int n, double *out, void *) {
-    if (!c || n < 1 || n > (int)c->partials.size() || !out) return fail(MGK_EINVAL, "mgk_partials_finish");
+    if (!c || n < 1 || n > c->max_partials || !out) return fail(MGK_EINVAL, "mgk_partials_finish");
     double s = 0; for (int q = 0; q < n; q++) s += c->partials[q];
     deliver(c, s, out);
     return 0;
@@ -670,7 +681,7 @@ int mgk_prolong_jacobi2_slab_f64(mgk_ctx *c, const mgk_geom *gf, const mgk_geom 
 }
 int mgk_jacobi2_sumsq_mid_slab_f64(mgk_ctx *c, const mgk_geom *g, const mgk_geom *gf, const double *coef, double dinv, double scale, const double *b, const double *u, double *o,
                                    const double *far, int lo, int hi, int z0, int z1, int part_off, int *nparts, void *) {
-    if (!c || !g || g->dim != 3 || !coef || !b || !u || !o || u == o || !nparts || part_off < 0 || part_off >= (int)c->partials.size()) return fail(MGK_EINVAL, "mgk_jacobi2_sumsq_mid_slab_f64");
+    if (!c || !g || g->dim != 3 || !coef || !b || !u || !o || u == o || !nparts || part_off < 0 || part_off >= c->max_partials) return fail(MGK_EINVAL, "mgk_jacobi2_sumsq_mid_slab_f64");
     if (z0 < 0 || z1 > g->nz || z0 >= z1) return fail(MGK_EINVAL, "mgk_jacobi2_sumsq_mid_slab_f64: range");
     __atomic_fetch_add(&g_calls_mid_slab, 1, __ATOMIC_RELAXED);
     int rc = jacobi2_api<double>(c, g, gf, coef, dinv, scale, b, u, o, far, lo, hi, z0, z1);
@@ -694,7 +705,7 @@ static void print_stats() { if (getenv("MOCK_MGK_STATS")) fprintf(stderr, "MOCK_
 static struct StatsAtExit { StatsAtExit() { atexit(print_stats); } } g_stats_at_exit;
 int mgk_jacobi2_sumsq_slab_f64(mgk_ctx *c, const mgk_geom *g, const mgk_geom *gf, const double *coef, double dinv, double scale, const double *b, const double *u, double *o,
                                const double *far, int lo, int hi, int z0, int z1, int part_off, int *nparts, void *) {
-    if (!c || !g || g->dim != 3 || !coef || !b || !u || !o || u == o || !nparts || part_off < 0 || part_off >= (int)c->partials.size()) return fail(MGK_EINVAL, "mgk_jacobi2_sumsq_slab_f64");
+    if (!c || !g || g->dim != 3 || !coef || !b || !u || !o || u == o || !nparts || part_off < 0 || part_off >= c->max_partials) return fail(MGK_EINVAL, "mgk_jacobi2_sumsq_slab_f64");
     if (z0 < 0 || z1 > g->nz || z0 >= z1) return fail(MGK_EINVAL, "mgk_jacobi2_sumsq_slab_f64: range");
     __atomic_fetch_add(&g_calls_j2n_slab, 1, __ATOMIC_RELAXED);
     std::vector<double> r(g->total, 0.0);

@@ -8,6 +8,8 @@ padding of the allocation are zero.  The contract this pins is the one of includ
 
 CASES: (body, args, covers) -- covers: the entry points the case is there for; each must appear in the proxy's call log and, at least once, be
 handed an output that still holds the poison (many bodies clear their outputs with mgk_memset0 and reuse them: the proxy poisons them again).
+Before every call of a reducing entry point (guarded.REDUCERS) the proxy fills the context's whole reduction scratch with the poison too: a partial
+slot that the finishing kernel adds up and the launch did not write turns the sum the body compares into NaN (tests/test_reduction_scratch_gpu.py).
 The exceptions are tables with reasons: UNPOISONED (cases that run with the poison off: a body that asserts the zeros of its own memset), IN_PLACE
 (entry points whose field is input and output at once, or whose output is no field), OWN_FRAMES and OWN_FILL (bodies that lay their own sentinels
 instead).  Shapes: per
@@ -36,7 +38,7 @@ import test_kernels_gpu as K
 import test_mixed_gpu as MX
 import test_mixed_width_gpu as MW
 import test_three_sweeps_gpu as T3
-from guarded import EXEMPT, Guarded, layout          # EXEMPT: the field writers no case here is there for, with the reasons
+from guarded import EXEMPT, REDUCERS, Guarded, layout          # EXEMPT: the field writers no case here is there for, with the reasons
 from multigrid_petsc_amd.mgk import Geom
 from oracle import Oracle
 
@@ -432,6 +434,9 @@ def run_case(mgk, orc, body, args, covers, have=None):
         called = set(G.calls)
         assert covers <= called, f"the case is there for {sorted(covers - called)}, which the body never called"
         G.assert_no_leaks()
+        if G.poison:                                   # every reducing call of the body found the whole reduction scratch poisoned (the later ranges of a group excepted)
+            dry = sorted(r for r in called & set(REDUCERS) if not G.scratch_poisoned_calls.get(r))
+            assert not dry, f"the reduction scratch was not poisoned before any call of {dry}"
         if body in OWN_FRAMES:
             # no field(g) output to poison or to frame-check: the body lays its own sentinels around compact or raw images and compares every
             # byte of the whole allocation, which the proxy hands it after the guard check
