@@ -28,8 +28,15 @@
  *   x ghosts inside the row padding (j=-1, j=nx).  Ghosts of a global boundary
  *   hold 0 (homogeneous Dirichlet, src/solver.c:239-251 drops those
  *   neighbours); ghost planes of an internal slab boundary hold halo data.
- *   The row starts 128-byte aligned; j=0 sits at column MGK_XOFF so that the
- *   nx+1 = 2^m doubles (interior + right ghost) of a row are whole 128-B lines.
+ *   The row starts 128-byte aligned and j=0 sits at column MGK_XOFF, a whole
+ *   number of 128-B lines in: pitch = MGK_XOFF + nx + 1 rounded up to 16 doubles
+ *   (fp32: 32 + nx + 1 rounded up to 32 floats).  nx is odd, so a row's nx+1
+ *   elements (interior + right ghost) are aligned pairs; they are whole 128-B
+ *   lines when nx+1 is a multiple of 16, and whole wave rows (128 doubles / 256
+ *   floats per wave) only at some widths.  nx+1 need not be 2^m: the full-row
+ *   kernel forms are taken where a row is 1, 2, 4 or 8 whole wave rows, every
+ *   other width runs the predicated forms; the _ok_ queries tell where a fused
+ *   entry point is offered.
  */
 #ifndef MGK_H
 #define MGK_H

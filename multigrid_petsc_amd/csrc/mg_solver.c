@@ -353,7 +353,8 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         int n = mg_grid_n(cfg->npts, l);
         int f = 1 << l;
         if (n < 1 || (cfg->npts - 1) % f != 0 || (n & 1) == 0)
-            return mgfail(MGK_EINVAL, "mg_solver_create: npts-1 must be 2^m with m >= levels (vertex-centred coarsening, src/matbuild.c:62-66)");
+            return mgfail(MGK_EINVAL, "mg_solver_create: npts-1 must be divisible by 2^(levels-1) and every level must keep an odd number >= 1 of "
+                                      "unknowns per axis, (npts-1)/2^l - 1 (vertex-centred coarsening, src/matbuild.c:62-66)");
     }
     if (cfg->mesh != 0 && (cfg->mesh < 0 || cfg->mesh > 2 || cfg->dim != 2 || cfg->precision != MG_PREC_FP64 || cfg->nranks > 1))
         return mgfail(MGK_EINVAL, "mg_solver_create: -mesh 1/2 is built for 2-D, fp64, one GPU");

@@ -2249,8 +2249,7 @@ static int jacobi2(mgk_ctx *c, const mgk_geom *g, const double *coef, double din
     hipStream_t s = S(c, stream);
     if (norm_parts) {
         // with the residual norm of the input field: the register form on full-row shapes only
-        constexpr int WRn = 64 * VX;
-        if (sizeof(T) != 8 || (g->nx + 1) % WRn != 0 || (g->ny + 1) % 4 != 0 || part_off < 0)
+        if (sizeof(T) != 8 || !whole_rows_1248(g, 64 * VX) || (g->ny + 1) % 4 != 0 || part_off < 0)
             return fail(MGK_EINVAL, "mgk_jacobi2_sumsq: built for fp64 full-row shapes (n = 127, 255, 511, 1023)");
         if ((long)nblk > c->max_partials - part_off) return fail(MGK_EINVAL, "mgk_jacobi2_sumsq: more blocks than partial slots");
         a.partials = c->partials + part_off;
@@ -2268,8 +2267,8 @@ static int jacobi2(mgk_ctx *c, const mgk_geom *g, const double *coef, double din
     // 0.72 ms; fp32 1023^3: 3.98 vs 7.29 ms, the register variant is at the 256-VGPR limit there)
     const bool ring = (g_variant == 1) || (g_variant == MGK_TUNE_J2_RING_PRED) || (g_variant != 2 && g_variant != MGK_TUNE_J2_REG_PRED && !(sizeof(T) == 8 && w > 4));
     // full-row shapes: unconditional loads + DPP lane shifts (MGK_TUNE_J2_REG_PRED / _RING_PRED keep the predicated / ds_bpermute form)
-    constexpr int WR = 64 * VX;
-    const bool full = (g->nx + 1) % WR == 0 && (g->ny + 1) % 4 == 0 && g_variant != MGK_TUNE_J2_REG_PRED && g_variant != MGK_TUNE_J2_RING_PRED;
+    // (whole_rows_1248: a row of 3, 5, 6 or 7 waves runs in a block of 4 or 8 and takes the predicated form)
+    const bool full = whole_rows_1248(g, 64 * VX) && (g->ny + 1) % 4 == 0 && g_variant != MGK_TUNE_J2_REG_PRED && g_variant != MGK_TUNE_J2_RING_PRED;
     if (zero_guess) {
         if (!full || far_lo || far_hi || norm_parts) return fail(MGK_EINVAL, "mgk_jacobi2_zero: built for whole grids of full-row shape (the LDS-ring form of the two-sweep kernel)");
         if (g_variant == MGK_TUNE_J2_RING_OLD || (sizeof(T) == 8 && g_variant != MGK_TUNE_J2_ZERO_RINGB)) {   // the form before the instruction diet; fp64 keeps it
@@ -2312,27 +2311,28 @@ extern "C" int mgk_jacobi2_f32(mgk_ctx *c, const mgk_geom *g, const double *coef
 template <typename T>
 static bool j2zero_ok(const mgk_geom *g) {
     constexpr int VX = 16 / sizeof(T);
-    if (!g || g->dim != 3 || (g->nx + 1) % (64 * VX) != 0 || (g->ny + 1) % 4 != 0 || g->nx + 1 > 1024) return false;
-    const int w = (g->nx + 1) / (64 * VX);
-    if (g_variant == 2 || g_variant == MGK_TUNE_J2_REG_PRED || g_variant == MGK_TUNE_J2_RING_PRED) return false;
-    return w == 1 || w == 2 || w == 4 || w == 8;                 // (fp64 rows of 1024 too: the ring form, 148 KB of LDS, only from the zero guess)
+    if (!g || g->dim != 3 || !whole_rows_1248(g, 64 * VX) || (g->ny + 1) % 4 != 0 || g->nx + 1 > 1024) return false;
+    // (fp64 rows of 1024 too: the ring form, 148 KB of LDS, only from the zero guess)
+    return !(g_variant == 2 || g_variant == MGK_TUNE_J2_REG_PRED || g_variant == MGK_TUNE_J2_RING_PRED);
 }
 extern "C" int mgk_jacobi2_zero_ok_f64(const mgk_geom *g) { return j2zero_ok<double>(g) ? 1 : 0; }
 extern "C" int mgk_jacobi2_zero_ok_f32(const mgk_geom *g) { return j2zero_ok<float>(g) ? 1 : 0; }
 extern "C" int mgk_jacobi2_zero_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                                     const double *b, double *unew, void *stream) {
     if (!g) return fail(MGK_EINVAL, "mgk_jacobi2_zero_f64: bad arguments");
+    if (!j2zero_ok<double>(g)) return fail(MGK_EINVAL, "mgk_jacobi2_zero_f64: shape or tuning variant not offered (mgk_jacobi2_zero_ok_f64 tells)");
     return jacobi2<double>(c, g, coef, dinv, scale, b, nullptr, unew, nullptr, nullptr, 0, g->nz, stream, nullptr, 0, true);
 }
 extern "C" int mgk_jacobi2_zero_f32(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                                     const float *b, float *unew, void *stream) {
     if (!g) return fail(MGK_EINVAL, "mgk_jacobi2_zero_f32: bad arguments");
+    if (!j2zero_ok<float>(g)) return fail(MGK_EINVAL, "mgk_jacobi2_zero_f32: shape or tuning variant not offered (mgk_jacobi2_zero_ok_f32 tells)");
     return jacobi2<float>(c, g, coef, dinv, scale, b, nullptr, unew, nullptr, nullptr, 0, g->nz, stream, nullptr, 0, true);
 }
 // Two sweeps AND || b - A u ||^2 of the input field (formed by the first sweep anyway): closes cycle k (src/solver.c:1545-1546)
 // and makes the first two pre-smoothing sweeps of cycle k+1 (:1531) in one pass.  unew is only adopted if another cycle runs.
 extern "C" int mgk_jacobi2_sumsq_ok_f64(const mgk_geom *g) {
-    return (g && g->dim == 3 && (g->nx + 1) % 128 == 0 && (g->ny + 1) % 4 == 0 && g->nx + 1 <= 1024) ? 1 : 0;
+    return (g && g->dim == 3 && whole_rows_1248(g, 128) && (g->ny + 1) % 4 == 0 && g->nx + 1 <= 1024) ? 1 : 0;
 }
 extern "C" int mgk_jacobi2_sumsq_f64(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale,
                                      const double *b, const double *u, double *unew, double *sumsq_host, void *stream) {

@@ -22,6 +22,15 @@ template <int... WXS, typename F> static inline void with_width(int w, F &&f) { 
 // ring depth of the line marches: the knob's value `d` (line_depth(), xline_depth()) picks the built D equal to it, the last one listed otherwise
 template <int... DS, typename F> static inline void with_depth(int d, F &&f) { with_listed<Equals, DS...>(d, f); }
 template <typename F> static inline void width_1248(int w, F &&f) { with_width<1, 2, 4, 8>(w, f); }
+// whole rows: the nx + 1 elements of a row (interior + right ghost) are a whole number of wave rows (wave_row = 64 lanes x the lane's vector)
+// AND that number is a block width width_1248 builds.  Only then is a block exactly one row wide, which the full-row kernel forms lean on:
+// unconditional loads and stores in x, the last lane of the block as the owner of the ghost column, zero pads at the two ends of the block.
+// Rows of 3, 5, 6 or 7 waves (nx = 383, 639, 767, 895 in fp64) run in the next wider block and must take the predicated forms.
+static inline bool whole_rows_1248(const mgk_geom *g, int wave_row) {
+    if (!g || (g->nx + 1) % wave_row != 0) return false;
+    const int w = (g->nx + 1) / wave_row;
+    return w == 1 || w == 2 || w == 4 || w == 8;
+}
 template <typename F> static inline void width_48(int w, F &&f) { with_width<4, 8>(w, f); }      // the pj2 kernels: rows of 512 / 1024 only
 // LAUNCH_WX(width_1248, w, (k_foo<T, WX, 3>), nblk, stream, args...): blocks of 64 * WX threads; `kernel` names WX
 #define LAUNCH_WX(pick, w, kernel, nblk, s, ...)                                                      \

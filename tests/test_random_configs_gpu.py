@@ -25,6 +25,16 @@ def test_random_solver_configurations_equal_the_oracle():
 
 
 @pytest.mark.timeout(600)
+def test_random_off_width_solver_configurations_equal_the_oracle():
+    """the same draws with the tool's off-width size lists: npts - 1 = 3, 5 or 7 times a power of two, the depth up to the deepest hierarchy
+    mg_solver_create accepts (level widths 11, 23, 47, 95, 191, 383, 639, 767, 895: no whole number of wave rows, or 3, 5, 6, 7 of them)"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "stress_solver.py"), "40", "13", "problem", "offwidth"], stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=500, cwd=ROOT)
+    assert p.returncode == 0 and "40 configurations, 0 mismatches" in p.stdout, p.stdout[-3000:]
+    assert "REFUSED" not in p.stdout, p.stdout[-3000:]
+
+
+@pytest.mark.timeout(600)
 def test_random_slab_configurations_equal_the_oracle():
     _run("stress_slabs.py", 20, 5, 500)
 

@@ -8,7 +8,11 @@ usage: stress_solver_mock.py [count] [seed] [problem|rhs]
 The third argument is the right-hand-side mode.  problem (default): the manufactured right-hand side (mg_solver_set_rhs_problem), every draw as it has
 always been.  rhs: the same draws, and from a SEPARATE generator a right-hand side of tests/rhs_cases.py (rough uniform data / a handful of spikes)
 loaded through mg_solver_set_rhs_host; half the draws then load a second, different right-hand side into the same, live solver object -- or go from the
-manufactured one to a host one or back -- and compare the second result with a fresh solver's (bit for bit, norms included) and with the oracle's."""
+manufactured one to a host one or back -- and compare the second result with a fresh solver's (bit for bit, norms included) and with the oracle's.
+usage: stress_solver_mock.py count seed problem|rhs offwidth
+The optional fourth argument swaps the size lists: every draw above takes npts = 2^k + 1; with `offwidth` npts - 1 is 3, 5 or 7 times a power of two
+(level widths 11, 23, 47, 95, ...: rows that are no whole number of wave rows, or a number of them that no block width matches) and the depth is
+drawn up to the deepest hierarchy mg_solver_create accepts for that size.  Without it every draw is what it has always been."""
 import ctypes
 import os
 import subprocess
@@ -130,6 +134,9 @@ def main(mock=True):
     if rhs_mode not in ("problem", "rhs"):
         sys.exit(f"right-hand-side mode {rhs_mode!r}: problem or rhs")
     rng2 = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 0x726873]) if rhs_mode == "rhs" else None
+    offwidth = len(sys.argv) > 4
+    if offwidth and sys.argv[4] != "offwidth":
+        sys.exit(f"size lists {sys.argv[4]!r}: offwidth, or nothing")
     if mock:
         inject()
     rhs_cases = __import__("rhs_cases") if rhs_mode == "rhs" else None      # (tests/rhs_cases.py: the rhs mode alone needs it)
@@ -139,11 +146,20 @@ def main(mock=True):
     bad = 0
     for q in range(count):
         dim = int(rng.choice([2, 3, 3]))
-        if mock:
+        if offwidth:
+            if mock:
+                npts = int(rng.choice([13, 25, 41, 49, 57, 81, 97] if dim == 2 else [13, 21, 25]))
+            else:
+                npts = int(rng.choice([13, 25, 41, 49, 97, 193, 385, 641, 769, 897] if dim == 2 else [13, 21, 25, 49, 97]))
+            lmax = 0                                         # the deepest hierarchy mg_solver_create takes: every level an odd width >= 1
+            while (npts - 1) % (1 << lmax) == 0 and ((npts - 1) >> lmax) - 1 >= 1 and (((npts - 1) >> lmax) - 1) & 1:
+                lmax += 1
+        elif mock:
             npts = int(rng.choice([9, 17, 33, 65, 129] if dim == 2 else [9, 17, 33]))
+            lmax = int(np.log2(npts - 1))
         else:
             npts = int(rng.choice([9, 17, 33, 65, 129, 257, 513, 1025] if dim == 2 else [9, 17, 33, 65, 129]))
-        lmax = int(np.log2(npts - 1))
+            lmax = int(np.log2(npts - 1))
         levels = int(rng.integers(1, lmax + 1))
         v0, v1 = int(rng.integers(0, 6)), int(rng.integers(1, 5))
         mesh = int(rng.choice([0, 0, 1, 2])) if dim == 2 else 0
