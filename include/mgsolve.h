@@ -208,6 +208,24 @@ int  mg_solver_solve_fmg(mg_solver *s, int nu);
  * mg_solver_destroy); if they do not fit the error names the restart length and the bytes and nothing stays allocated.
  * One GPU, fp64, Richardson + point Jacobi, any mesh, 2-D and 3-D, 1 <= restart <= MGK_KRYLOV_MAX - 1: anything else returns MGK_EINVAL. */
 int  mg_solver_solve_gmres(mg_solver *s, int restart);
+/* Conjugate gradients with the V-cycle as preconditioner (PETSc's -ksp_type cg -pc_type mg) on the current right-hand side, for the uniform
+ * mesh, where the fine-level operator A and the cycle M (one V-cycle from the zero guess) are both symmetric:
+ *   x = 0, r = b, z = M r, p = z, rho = r . z;
+ *   step k: q = A p, sigma = p . q, alpha = rho / sigma; x += alpha p, r -= alpha q, rnorm[k] = ||r||;
+ *           stop, or z = M r, rho' = r . z, beta = rho' / rho, p = z + beta p, rho = rho'.
+ * Every product and sum is rounded separately (no FMA).  Stops when rnorm[k] <= rtol ||b||, after maxiter steps, or under the divergence
+ * guard of mg_solver_solve.  A BREAKDOWN -- alpha not finite or <= 0, beta not finite or < 0: M is indefinite, as with an over-relaxed
+ * smoother -- ends the iteration like a stop: the return code is 0, the history ends at the last completed step and the solution is that
+ * step's x; mg_solver_cg_breakdown tells the step.  On return: the solution is x, level 0's right-hand side is the caller's, iterations =
+ * CG steps, rnorm[0] = ||b||, solve_seconds covers the call; reset + solve then behave as on a fresh solver.  ||b|| = 0 or maxiter < 1: the
+ * solution is 0, no step.  The first call allocates five fine-level fields whatever the step count (freed by mg_solver_destroy); if they do
+ * not fit the error names the count and the bytes and nothing stays allocated.  Per step: one cycle, 96 B per fine unknown in three
+ * launches, three host synchronisations.
+ * One GPU, fp64, Richardson + point Jacobi, the uniform mesh (mesh == 0; elsewhere use mg_solver_solve_gmres), 2-D and 3-D: anything else
+ * returns MGK_EINVAL with a message of its own. */
+int  mg_solver_solve_cg(mg_solver *s);
+/* the step (1-based) in which the last mg_solver_solve_cg broke down; 0: it did not */
+int  mg_solver_cg_breakdown(const mg_solver *s);
 /* block until every stream of this solver's device is idle */
 int  mg_solver_sync(mg_solver *s);
 

@@ -523,6 +523,9 @@ void mg_solver_destroy(mg_solver *s) {
         if (s->pin) mgk_host_free(s->ctx, s->pin);
         for (int q = 0; q < s->gm_nfields; q++) if (s->gm_field[q]) mgk_free(s->ctx, s->gm_field[q]);
         if (s->gm_hdev) mgk_free(s->ctx, s->gm_hdev);
+        for (int q = 0; q < MG_CG_FIELDS; q++) if (s->cg_field[q]) mgk_free(s->ctx, s->cg_field[q]);
+        if (s->cg_rho_dev) mgk_free(s->ctx, s->cg_rho_dev);
+        if (s->cg_ws && s->cg_ws_free) s->cg_ws_free(s->ctx, s->cg_ws);
         for (int p = 0; p < 2; p++) if (s->coarse_graph[p]) mgk_graph_destroy(s->ctx, s->coarse_graph[p]);
         for (int l = 0; l < s->levels; l++) {
             mg_level *L = &s->L[l];

@@ -1,7 +1,7 @@
 /*
- * mg_solver_internal.h -- the solver's state and the cycle steps that the full-multigrid driver (mg_fmg.c) and the GMRES driver (mg_gmres.c)
- * build on.  Private to libmgpetsc.so: not installed, not part of the C API (include/mgsolve.h).  Everything declared here is DEFINED in
- * mg_solver.c, which references no symbol of mg_fmg.c or mg_gmres.c (the host tests link mg_solver.c without them, against a mock of the
+ * mg_solver_internal.h -- the solver's state and the cycle steps that the full-multigrid driver (mg_fmg.c), the GMRES driver (mg_gmres.c)
+ * and the CG driver (mg_cg.c) build on.  Private to libmgpetsc.so: not installed, not part of the C API (include/mgsolve.h).  Everything declared here is DEFINED in
+ * mg_solver.c, which references no symbol of mg_fmg.c, mg_gmres.c or mg_cg.c (the host tests link mg_solver.c without them, against a mock of the
  * kernel ABI).
  */
 #ifndef MG_SOLVER_INTERNAL_H
@@ -12,6 +12,7 @@
 
 #define MG_MAX_LEVELS 32
 #define MG_MAX_TIMERS 4096
+#define MG_CG_FIELDS 5
 
 /* fuse bits mg_solver_create clears (include/mgsolve.h: mg_fuse_bits) */
 /* y-line Jacobi: every pass that bakes POINT Jacobi into its kernel (bits 1, 3, 5, 8-15); the fused residual + norm and residual + restriction stay */
@@ -104,6 +105,14 @@ struct mg_solver {
     void *gm_field[MGK_KRYLOV_MAX + 3];
     int gm_nfields, gm_restart;
     double *gm_hdev;
+    /* conjugate gradients (mg_cg.c): x, p, the other p, q and the caller's b, the device slot of r . z and the reduction workspace of the two
+     * fused passes, allocated at the first mg_solver_solve_cg; freed by mg_solver_destroy, the workspace through cg_ws_free (set by mg_cg.c,
+     * the only file that knows what it is) */
+    void *cg_field[MG_CG_FIELDS];
+    double *cg_rho_dev;
+    void *cg_ws;
+    void (*cg_ws_free)(mgk_ctx *ctx, void *ws);
+    int cg_breakdown;       /* the step (1-based) in which the last mg_solver_solve_cg broke down; 0: none */
 };
 
 /* KSPCHEBYSHEV on the fused cycle (fuse bit 15): mg_cheby.c holds the only calls of the mgk_cheby3_2d_* / mgk_tail_cycle_cheby_f64 kernels.
@@ -165,7 +174,7 @@ int    mgi_vcycle_rooted(mg_solver *s, int l);           /* one V-cycle on the l
 int    mgi_vcycle_once(mg_solver *s);                    /* one iteration of the solve loop (cycle rooted at level 0 + the norm), iter += 1 */
 int    mgi_iterate(mg_solver *s);                        /* the solve loop under the stop rule of src/solver.c:1530, from the current state */
 int    mgi_finalize(mg_solver *s);                       /* materialise the iterate the last norm belongs to */
-/* the V-cycle as a linear operator (mg_gmres.c): ONE cycle rooted at level 0 from the zero guess on whatever level 0's b holds, no norm; the
+/* the V-cycle as a linear operator (mg_gmres.c, mg_cg.c): ONE cycle rooted at level 0 from the zero guess on whatever level 0's b holds, no norm; the
  * complete iterate lands in level 0's u (no sweep stays owed).  Every flag is reset as mgi_start does; the coarse-level graph and the LDS tail
  * are used */
 int    mgi_apply_cycle(mg_solver *s);

@@ -266,6 +266,25 @@ def _sigs(L):
     return S
 
 
+def cg_sigs(L):
+    """include/mgk_cg.h: the two fused passes of the CG driver and their reduction workspace, bound on first use (the stand-in libraries of
+    the host tests need not have them)"""
+    vp, i, d = C.c_void_p, C.c_int, C.c_double
+    G = C.POINTER(Geom)
+    S = {
+        "mgk_cg_workspace_create": (i, [vp, C.POINTER(vp)]),
+        "mgk_cg_workspace_destroy": (None, [vp, vp]),
+        "mgk_cg_workspace_debug": (i, [vp, C.POINTER(vp), C.POINTER(i)]),
+        # (coef, beta, z, p_old or None, p_new, q, ws, sigma or None) / (alpha, p, q, x, r, ws, sumsq or None)
+        "mgk_cg_direction_apply_dot_f64": (i, [vp, G, c_dp, d, vp, vp, vp, vp, vp, C.POINTER(d), vp]),
+        "mgk_cg_update_sumsq_f64": (i, [vp, G, d, vp, vp, vp, vp, vp, C.POINTER(d), vp]),
+    }
+    for name, (res, args) in S.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = res, args
+    return S
+
+
 class Mgk:
     """Thin object wrapper: one context on one device."""
 

@@ -139,6 +139,17 @@ def _gmres_lib(L):
     return L
 
 
+def _cg_lib(L):
+    """the CG entry points, bound on first use like the GMRES one"""
+    if not getattr(L, "_mg_cg_sigs", False):
+        L.mg_solver_solve_cg.restype = C.c_int
+        L.mg_solver_solve_cg.argtypes = [C.c_void_p]
+        L.mg_solver_cg_breakdown.restype = C.c_int
+        L.mg_solver_cg_breakdown.argtypes = [C.c_void_p]
+        L._mg_cg_sigs = True
+    return L
+
+
 def get_ranges(totaln, procs):
     r = np.zeros(procs + 1, dtype=np.int32)
     _lib().mg_get_ranges(totaln, procs, r.ctypes.data_as(C.c_void_p))
@@ -226,6 +237,18 @@ class Solver:
         Arnoldi steps; rnorm[k] is the residual estimate after step k"""
         self._chk(_gmres_lib(self.L).mg_solver_solve_gmres(self.h, restart))
         return self.iterations
+
+    def solve_cg(self):
+        """conjugate gradients with the V-cycle as preconditioner (PETSc's -ksp_type cg -pc_type mg; uniform mesh, point Jacobi); returns
+        the number of CG steps; rnorm[k] is the norm of the recurrence residual after step k.  A breakdown ends the iteration like a stop:
+        see cg_breakdown"""
+        self._chk(_cg_lib(self.L).mg_solver_solve_cg(self.h))
+        return self.iterations
+
+    @property
+    def cg_breakdown(self):
+        """the step (1-based) in which the last solve_cg broke down (alpha not finite or <= 0, beta not finite or < 0); 0: it did not"""
+        return _cg_lib(self.L).mg_solver_cg_breakdown(self.h)
 
     def sync(self):
         self._chk(self.L.mg_solver_sync(self.h))
