@@ -221,11 +221,24 @@ int  mg_solver_solve_gmres(mg_solver *s, int restart);
  * solution is 0, no step.  The first call allocates five fine-level fields whatever the step count (freed by mg_solver_destroy); if they do
  * not fit the error names the count and the bytes and nothing stays allocated.  Per step: one cycle, 96 B per fine unknown in three
  * launches, three host synchronisations.
- * One GPU, fp64, Richardson + point Jacobi, the uniform mesh (mesh == 0; elsewhere use mg_solver_solve_gmres), 2-D and 3-D: anything else
- * returns MGK_EINVAL with a message of its own. */
+ * One GPU, fp64 (a mixed-precision solver: mg_solver_solve_cg_mixed), Richardson + point Jacobi, the uniform mesh (mesh == 0; elsewhere use
+ * mg_solver_solve_gmres), 2-D and 3-D: anything else returns MGK_EINVAL with a message of its own. */
 int  mg_solver_solve_cg(mg_solver *s);
-/* the step (1-based) in which the last mg_solver_solve_cg broke down; 0: it did not */
+/* the step (1-based) in which the last mg_solver_solve_cg or mg_solver_solve_cg_mixed broke down; 0: it did not */
 int  mg_solver_cg_breakdown(const mg_solver *s);
+/* The same conjugate gradients in fp64 on a solver created with precision = MG_PREC_MIXED, preconditioned by the fp32 V-cycle its plain
+ * iteration runs between two defect corrections: M r = (double) Vcycle32((float) r) from the zero guess.
+ *   x = 0, r = b, r32 = (float) r, z32 = Vcycle32(r32), rho = sum r * (double) z32;
+ *   step k: p = (double) z32 + beta p, q = A p, sigma = p . q, alpha = rho / sigma; x += alpha p, r -= alpha q, rnorm[k] = ||r||, r32 = (float) r;
+ *           stop, or z32 = Vcycle32(r32), rho' = sum r * (double) z32, beta = rho' / rho, rho = rho'.
+ * x, r, p, q, A and every sum are fp64, rounded as in mg_solver_solve_cg; (float) rounds to nearest, (double) is exact.  The stop rule, the
+ * breakdown semantics (mg_solver_cg_breakdown), what is left in the solution, the right-hand side, rnorm, iterations and solve_seconds,
+ * ||b|| = 0 or maxiter < 1, reset + solve afterwards and the five fine-level fields of the first call are those of mg_solver_solve_cg (the two
+ * entry points share the fields).  The fp32 cycle is symmetric to about 3e-7 only; at rtol 1e-7 the step counts are those of fp64 CG.  Per step:
+ * one fp32 cycle and 92-96 B per fine unknown in three launches, three host synchronisations.
+ * A mixed-precision solver (3-D), one GPU, Richardson + point Jacobi, the uniform mesh: anything else returns MGK_EINVAL with a message of its
+ * own. */
+int  mg_solver_solve_cg_mixed(mg_solver *s);
 /* block until every stream of this solver's device is idle */
 int  mg_solver_sync(mg_solver *s);
 

@@ -12,7 +12,8 @@
  * iteration, -mg_gmres_restart m (default 30, PETSc's) its restart length; "Number of iterations" then counts Arnoldi steps and rData.dat
  * holds the residual estimates.  Without the option nothing changes.
  * -mg_krylov cg: conjugate gradients with the V-cycle as preconditioner (PETSc's -ksp_type cg -pc_type mg; uniform mesh, point Jacobi);
- * "Number of iterations" then counts CG steps.  It excludes -mg_accel gmres; -mg_krylov none is the default.
+ * "Number of iterations" then counts CG steps.  It excludes -mg_accel gmres; -mg_krylov none is the default.  With -precision mixed (3-D) the
+ * fp64 recurrence is preconditioned by the fp32 V-cycle (mg_solver_solve_cg_mixed).
  * Output mirrors what the reference prints: the PrintInfo block (src/poisson.c:165-214), error[0..2]
  * (src/solver.c:1333), "Relative residual" (:1354), "Solver walltime" (:1572), and the five files of
  * Postprocessing (src/solver.c:160-164,1331-1353): eData.dat, rData.dat, and -- the O(N) text dumps --
@@ -30,6 +31,7 @@
 /* a driver linked without csrc/mg_gmres.c (the host tests link this file with mg_solver.c alone) still links: -mg_accel gmres is then refused */
 extern int mg_solver_solve_gmres(mg_solver *s, int restart) __attribute__((weak));
 extern int mg_solver_solve_cg(mg_solver *s) __attribute__((weak));          /* the same for csrc/mg_cg.c and -mg_krylov cg */
+extern int mg_solver_solve_cg_mixed(mg_solver *s) __attribute__((weak));    /* ... for csrc/mg_cg_mixed.c and -mg_krylov cg -precision mixed */
 
 typedef struct { char key[64], val[128]; } kv;
 static kv g_kv[128];
@@ -118,14 +120,16 @@ int main(int argc, char **argv) {
         else if (strcmp(v, "none")) { fprintf(stderr, "mgpoisson: -mg_krylov must be cg or none\n"); return 2; }
     }
     if (cg && gmres) { fprintf(stderr, "mgpoisson: -mg_krylov cg and -mg_accel gmres exclude each other\n"); return 2; }
-    if (cg && !mg_solver_solve_cg) { fprintf(stderr, "mgpoisson: this build has no CG (-mg_krylov cg)\n"); return 2; }
+    const int cgmixed = cg && c.precision == MG_PREC_MIXED;    /* ... on the fp32 cycle: mg_solver_solve_cg_mixed */
+    if (cgmixed && !mg_solver_solve_cg_mixed) { fprintf(stderr, "mgpoisson: this build has no mixed-precision CG (-mg_krylov cg -precision mixed)\n"); return 2; }
+    if (cg && !cgmixed && !mg_solver_solve_cg) { fprintf(stderr, "mgpoisson: this build has no CG (-mg_krylov cg)\n"); return 2; }
     int map = 2;                                       /* poisson.in:11 */
     if ((v = get("-map"))) map = atoi(v);
     if (map < 0 || map > 2) { fprintf(stderr, "mgpoisson: -map must be 0, 1 or 2 (src/poisson.c:190-192)\n"); return 2; }
 
     mg_solver *s = NULL;
     if (mg_solver_create(&s, &c, NULL)) { fprintf(stderr, "mgpoisson: %s\n", mg_last_error()); return 1; }
-    if (mg_solver_set_rhs_problem(s) || (cg ? mg_solver_solve_cg(s) : gmres ? mg_solver_solve_gmres(s, restart) : mg_solver_solve(s))) { fprintf(stderr, "mgpoisson: %s\n", mg_last_error()); return 1; }
+    if (mg_solver_set_rhs_problem(s) || (cgmixed ? mg_solver_solve_cg_mixed(s) : cg ? mg_solver_solve_cg(s) : gmres ? mg_solver_solve_gmres(s, restart) : mg_solver_solve(s))) { fprintf(stderr, "mgpoisson: %s\n", mg_last_error()); return 1; }
     const int it = mg_solver_iterations(s);
     const double *rn = mg_solver_rnorm(s);
     double err[3];

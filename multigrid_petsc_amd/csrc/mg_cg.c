@@ -31,7 +31,7 @@
 static int cg_check(const mg_solver *s) {
     if (!s) return mgi_fail(MGK_EINVAL, "mg_solver_solve_cg: null solver");
     if (s->cfg.nranks > 1) return mgi_fail(MGK_EINVAL, "mg_solver_solve_cg: built for one GPU (nranks == 1)");
-    if (s->cfg.precision != MG_PREC_FP64) return mgi_fail(MGK_EINVAL, "mg_solver_solve_cg: built for fp64 (not mixed precision)");
+    if (s->cfg.precision != MG_PREC_FP64) return mgi_fail(MGK_EINVAL, "mg_solver_solve_cg: built for fp64 (not mixed precision: use mg_solver_solve_cg_mixed)");
     if (s->cfg.ksp_type != MG_KSP_RICHARDSON) return mgi_fail(MGK_EINVAL, "mg_solver_solve_cg: built for Richardson + Jacobi (not Chebyshev)");
     if (s->cfg.pc_type != MG_PC_JACOBI)
         return mgi_fail(MGK_EINVAL, "mg_solver_solve_cg: built for point Jacobi (not the line or red-black Gauss-Seidel smoothers: their cycle is not symmetric)");
@@ -52,8 +52,9 @@ static void cg_free(mg_solver *s) {
     s->cg_ws = NULL;
 }
 
-/* x, p, the other p, q and the copy of b, the device slot of r . z and the reduction workspace: allocated at the first call */
-static int cg_alloc(mg_solver *s) {
+/* x, p, the other p, q and the copy of b, the device slot of r . z and the reduction workspace: allocated at the first call of either CG
+ * driver (mg_cg_mixed.c shares them) */
+int mgi_cg_alloc(mg_solver *s, const char *who) {
     if (s->cg_ws) return 0;
     CHK(mgk_sync(s->ctx, NULL));
     const size_t bytes = sizeof(double) * (size_t)s->L[0].f[0].g.total;
@@ -61,8 +62,8 @@ static int cg_alloc(mg_solver *s) {
     for (int q = 0; q < MG_CG_FIELDS; q++) {
         if (mgk_malloc(s->ctx, &s->cg_field[q], bytes)) {
             char msg[256];
-            snprintf(msg, sizeof(msg), "mg_solver_solve_cg: needs %d fine-level fields of %zu bytes (%.3f GB in all): the device could not "
-                     "allocate them", MG_CG_FIELDS, bytes, 1e-9 * (double)MG_CG_FIELDS * (double)bytes);
+            snprintf(msg, sizeof(msg), "%s: needs %d fine-level fields of %zu bytes (%.3f GB in all): the device could not "
+                     "allocate them", who, MG_CG_FIELDS, bytes, 1e-9 * (double)MG_CG_FIELDS * (double)bytes);
             cg_free(s);
             return mgi_fail(MGK_EINVAL, msg);
         }
@@ -72,7 +73,12 @@ static int cg_alloc(mg_solver *s) {
     int rc = mgk_malloc(s->ctx, &q, sizeof(double));
     s->cg_rho_dev = (double *)q;
     if (!rc) rc = mgk_cg_workspace_create(s->ctx, &ws);
-    if (rc) { cg_free(s); return mgi_fail(rc, "mg_solver_solve_cg: the reduction workspace"); }
+    if (rc) {
+        char msg[128];
+        snprintf(msg, sizeof(msg), "%s: the reduction workspace", who);
+        cg_free(s);
+        return mgi_fail(rc, msg);
+    }
     s->cg_ws = ws;
     return 0;
 }
@@ -124,7 +130,7 @@ static int cg_run(mg_solver *s) {
 int mg_solver_solve_cg(mg_solver *s) {
     int rc = cg_check(s);
     if (rc) return rc;
-    rc = cg_alloc(s);
+    rc = mgi_cg_alloc(s, "mg_solver_solve_cg");
     if (rc) return rc;
     mg_fset *F = &s->L[0].f[0];
     double ss = 0.0;

@@ -1872,6 +1872,21 @@ int mgi_apply_cycle(mg_solver *s) {
     return rc;
 }
 
+/* the fp32 cycle of a mixed-precision solver as a linear operator (mg_cg_mixed.c): e = Vcycle32(r32) from the zero guess on whatever level 0's
+ * fp32 b holds, into level 0's fp32 u -- cycle_body as the mixed iteration's vcycle_once runs it.  jz: level 0's fp32 tmp already holds the first
+ * sweep, scale * (r32 * dinv) (the caller's pass wrote it beside r32), under the condition of mgi_mixed_jz */
+int mgi_apply_cycle_f32(mg_solver *s, int jz) {
+    if (s->cfg.precision != MG_PREC_MIXED) return mgfail(MGK_EINVAL, "mgi_apply_cycle_f32: not a mixed-precision solver");
+    reset_level_flags(s);
+    s->spec_valid = 0; s->sweep_owed = 0; s->iterate_behind = 0;
+    s->L[0].f[1].jz_ready = jz && mgi_mixed_jz(s);
+    return cycle_body(s, 1, 1);
+}
+/* vcycle_once's condition for taking the fp32 cycle's first zero-guess sweep from the pass that produces r32 (fuse bit 8) */
+int mgi_mixed_jz(const mg_solver *s) {
+    return (s->cfg.fuse & MG_FUSE_COARSE_ZERO_SWEEP) && s->cfg.v[0] >= 1 && s->levels > 1 && !triple_ok(s, 1, 0, s->cfg.v[0]);
+}
+
 /* one iteration of the reference's loop (src/solver.c:1531-1543) on the levels l .. L-1 alone, level l in the role of level 0: v0 sweeps on
  * l from the guess in u_l (its KSP keeps the non-zero guess), the descent and the ascent as in cycle_body -- the tail kernel when l lies
  * above the tail, per-level launches otherwise -- but never the coarse-level graph (whose recording starts at level 0's cycle) */

@@ -178,4 +178,11 @@ int    mgi_finalize(mg_solver *s);                       /* materialise the iter
  * complete iterate lands in level 0's u (no sweep stays owed).  Every flag is reset as mgi_start does; the coarse-level graph and the LDS tail
  * are used */
 int    mgi_apply_cycle(mg_solver *s);
+/* the same for the fp32 cycle of a mixed-precision solver (mg_cg_mixed.c): level 0's fp32 b -> level 0's fp32 u, from the zero guess.  jz != 0:
+ * level 0's fp32 tmp holds the first sweep already; mgi_mixed_jz tells whether the cycle can take it (the condition of the mixed iteration) */
+int    mgi_apply_cycle_f32(mg_solver *s, int jz);
+int    mgi_mixed_jz(const mg_solver *s);
+/* the five fine-level fields, the device slot and the reduction workspace of the CG drivers (DEFINED in mg_cg.c, for mg_cg_mixed.c): allocated
+ * once; a failure names `who`, the count and the bytes and leaves nothing allocated */
+int    mgi_cg_alloc(mg_solver *s, const char *who);
 #endif

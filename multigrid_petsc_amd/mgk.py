@@ -285,6 +285,26 @@ def cg_sigs(L):
     return S
 
 
+def cg_mixed_sigs(L):
+    """include/mgk_cg_mixed.h: the three passes between the fp64 CG recurrence and the fp32 cycle, bound on first use; the workspace is the one of
+    cg_sigs"""
+    vp, i, d = C.c_void_p, C.c_int, C.c_double
+    G = C.POINTER(Geom)
+    S = {
+        # (g, g32, r, z32, ws, dot or None)
+        "mgk_cg_dot_f64_f32": (i, [vp, G, G, vp, vp, vp, C.POINTER(d), vp]),
+        # (g, g32, coef, beta, z32, p_old or None, p_new, q, ws, sigma or None)
+        "mgk_cg_direction_apply_dot_zf32_f64": (i, [vp, G, G, c_dp, d, vp, vp, vp, vp, vp, C.POINTER(d), vp]),
+        # (g, g32, alpha, p, q, x, r, r32, e0 or None, dinv, scale, ws, sumsq or None)
+        "mgk_cg_update_sumsq_f64_f32": (i, [vp, G, G, d, vp, vp, vp, vp, vp, vp, d, d, vp, C.POINTER(d), vp]),
+    }
+    cg_sigs(L)
+    for name, (res, args) in S.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = res, args
+    return S
+
+
 class Mgk:
     """Thin object wrapper: one context on one device."""
 

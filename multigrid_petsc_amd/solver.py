@@ -150,6 +150,15 @@ def _cg_lib(L):
     return L
 
 
+def _cg_mixed_lib(L):
+    """the entry point of CG over the fp32 cycle, bound on first use (a library built without mg_cg_mixed.c need not have it)"""
+    if not getattr(L, "_mg_cg_mixed_sigs", False):
+        L.mg_solver_solve_cg_mixed.restype = C.c_int
+        L.mg_solver_solve_cg_mixed.argtypes = [C.c_void_p]
+        L._mg_cg_mixed_sigs = True
+    return L
+
+
 def get_ranges(totaln, procs):
     r = np.zeros(procs + 1, dtype=np.int32)
     _lib().mg_get_ranges(totaln, procs, r.ctypes.data_as(C.c_void_p))
@@ -245,9 +254,15 @@ class Solver:
         self._chk(_cg_lib(self.L).mg_solver_solve_cg(self.h))
         return self.iterations
 
+    def solve_cg_mixed(self):
+        """solve_cg on a solver created with precision="mixed" (3-D): the fp64 recurrence preconditioned by the fp32 V-cycle,
+        M r = (double) Vcycle32((float) r); returns the number of CG steps; rnorm, cg_breakdown and the solution as after solve_cg"""
+        self._chk(_cg_mixed_lib(self.L).mg_solver_solve_cg_mixed(self.h))
+        return self.iterations
+
     @property
     def cg_breakdown(self):
-        """the step (1-based) in which the last solve_cg broke down (alpha not finite or <= 0, beta not finite or < 0); 0: it did not"""
+        """the step (1-based) in which the last solve_cg or solve_cg_mixed broke down (alpha not finite or <= 0, beta not finite or < 0); 0: it did not"""
         return _cg_lib(self.L).mg_solver_cg_breakdown(self.h)
 
     def sync(self):
