@@ -517,7 +517,9 @@ int  mgk_interp_jacobi3_2d_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom 
 /* the same in 3-D (whole grids, any vertex-centred shape): unew = J(J(J(u))) [and *sumsq_host = || b - A u ||^2 of the input field] in one
  * pass, 24 B per unknown.  Independent waves, one per SIMD (up to 512 registers per lane), 120 x 4 point columns per wave marching along z;
  * on rows of 512 / 1024 (nx = 511, 1023) the stacked form of include/mgk_sweep3.h, two waves per SIMD (MGK_TUNE_J3_3D_WAVES keeps the
- * independent waves there, MGK_TUNE_J3_3D_STACKED refuses every other shape). */
+ * independent waves there, MGK_TUNE_J3_3D_STACKED refuses every other shape).  The stacked form works on four rows per wave, with the
+ * norm as without; MGK_TUNE_J3S_NORM_R3 gives mgk_jacobi3_sumsq_f64 the three-row form it had before (the same field and the same
+ * residuals; the partial sums are per block, so the sum agrees to rounding, not bit for bit). */
 int  mgk_jacobi3_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef, double dinv, double scale,
                      const double *b, const double *u, double *unew, void *stream);
 int  mgk_jacobi3_sumsq_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef, double dinv, double scale,
@@ -748,6 +750,10 @@ enum mgk_tune {
     MGK_TUNE_NO_PROLONG_TRIPLE = 69    /* the prolongation + three-sweep pass (include/mgk_sweep3.h) is not offered: its _ok_ query answers 0 and the callers
                                           that ask it keep their two passes (the A/B switch of one build) */
 };
+/* the next value, beside the enum (whose enumerators and whose last value stay what they were): jacobi3_sumsq on rows of 512 / 1024, the stacked
+ * form with the norm of the input at THREE rows per wave (k_jacobi3s<3, 1>: 18 of a block's 24 rows stored) instead of four (26 of 32) -- the
+ * form before the accumulator pin, kept as the A/B switch of one build */
+#define MGK_TUNE_J3S_NORM_R3 70
 
 /* tuning knobs (profiling only), per calling thread: <=0 keeps the built-in choice.  They are GLOBAL to that thread, not per kernel -- set
  * them back to (-1, -1) after measuring one kernel.  The second argument, > 0, is the length of a chunk of the marching axis (planes, rows

@@ -88,6 +88,15 @@ typedef enum mg_fuse_bits {
 #define MG_FUSE_TRIPLE_MID 65536
 /* what mg_config.fuse = -1 selects: MG_FUSE_DEFAULT and bit 16 */
 #define MG_FUSE_AUTO (MG_FUSE_DEFAULT | MG_FUSE_TRIPLE_MID)
+/* (bit 17, 131072; not part of MG_FUSE_AUTO: mg_config.fuse = -1 adds it per width, where level 0 has rows of 1024 -- the gate of
+ * profiles/triple_norm/README.md is met there and not at rows of 512, where the bit is opt-in.  Where bit 16 runs its 75-byte passes -- fp64, 3-D, one rank, Richardson + point Jacobi,
+ * v0 = 3, level 0 a 511- / 1023-wide whole grid outside the coarse-level graph and not feeding it) the 66-byte level of DESIGN.md section 4
+ * (xxii): post- and pre-smoothing as two stacked passes and the plain residual + restriction,
+ * (P + S1, S2, S3)(N + S1', S2', S3')(R) = 25 + 24 + 17 B per fine unknown and cycle.  Level 0's post-smoothing is the prolongation +
+ * three-sweep pass in every cycle, so no sweep is owed and u is the iterate the norm belongs to; the pass that evaluates the norm
+ * (mgk_jacobi3_sumsq_f64) makes all three pre-smoothing sweeps of the next cycle.  The closing cycle of a call and a cycle that has no
+ * speculative sweeps to adopt keep their passes.  Same iterates bit for bit; the norms are those of the stored iterate, summed per block */
+#define MG_FUSE_TRIPLE_NORM 131072
 
 /* options of the reference driver (src/poisson.c:51-59, poisson.in) + the PETSc options that
  * KSPSetFromOptions (src/solver.c:1476,1492,1509) would pick up for the smoother */
@@ -108,7 +117,7 @@ typedef struct mg_config {
                          * (below that a slab sweep is shorter than the latency of its halo exchange) */
     int fuse;           /* which fused passes a cycle may use: a mask of mg_fuse_bits (above).  Every bit exists so that tests can run the
                          * unfused path as the reference; which path runs is otherwise decided by what the solver sees (dimension, v0,
-                         * ranks).  -1 selects the default set, MG_FUSE_AUTO */
+                         * ranks).  -1 selects the default set, MG_FUSE_AUTO, and MG_FUSE_TRIPLE_NORM with it in 3-D at npts = 1025 */
     int overlap;        /* nranks > 1: halo of sweep k on the comm stream while sweep k's interior runs; default on (-1) */
     int graph;          /* replay the launch-bound coarse levels as one captured HIP graph; default on (-1) */
     int pair_min_n;     /* levels with n >= pair_min_n run their sweeps two per pass (fuse bit 5); <=0: default 255 (3-D), 2047 (2-D) */
@@ -256,6 +265,11 @@ void *mg_solver_debug_kernel_ctx(mg_solver *s);
 int  mg_solver_tail_level(const mg_solver *s);
 /* launches of the prolongation + three-sweep pass (fuse bit 16) on a level since the solver was created */
 int  mg_solver_prolong_triple_launches(const mg_solver *s, int level);
+/* launches of the norm + three-sweep pass of level 0 (fuse bit 17) since the solver was created */
+int  mg_solver_triple_norm_launches(const mg_solver *s);
+/* recordings of the coarse-level graph thrown away since the solver was created because the level that feeds it had swapped u / tmp an odd
+ * number of times since the recording (0 in every default configuration) */
+int  mg_solver_graph_rerecorded(const mg_solver *s);
 int  mg_solver_level_n(const mg_solver *s, int level);              /* unknowns per side */
 int  mg_solver_level_local_planes(const mg_solver *s, int level, int *z0);
 long mg_solver_local_unknowns(const mg_solver *s);
@@ -271,7 +285,7 @@ int  mg_solver_error_norms(mg_solver *s, double err[3]);
 int  mg_solver_profile(mg_solver *s, int enable);
 int  mg_solver_profile_read(mg_solver *s, double *total_ms, int *launches);
 /* the same for one kind of launch: 0 = plain fine-level sweeps, 1 = two-sweeps-in-one-pass launches (in the 75-byte cycle of fuse bit 16: the
- * prolongation + two sweeps pass, the only one left on level 0), 2 = the three-sweep pass of fuse bit 16 */
+ * prolongation + two sweeps pass, the only one left on level 0), 2 = the three-sweep pass of fuse bit 16 / the norm + three-sweep pass of bit 17 */
 int  mg_solver_profile_read_kind(mg_solver *s, int kind, double *total_ms, int *launches);
 
 /* integer half of the reference (src/matbuild.c), implicit form */

@@ -370,7 +370,11 @@ int mg_solver_create(mg_solver **out, const mg_config *cfg, mg_comm *comm) {
         const int n0 = mg_grid_n(cfg->npts, 0);
         s->cfg.dist_min_n = n0 < 255 ? n0 : 255;
     }
+    /* -1: MG_FUSE_AUTO and, per width, bit 17 (MG_FUSE_TRIPLE_NORM) where level 0 has rows of 1024: the gate of profiles/triple_norm/README.md is met
+     * there (14.13 against 15.08 ms for level 0's three passes) and not at rows of 512 (1.85 against 1.95 ms: under the margin), where the bit stays opt-in */
+    const int fuse_by_default = s->cfg.fuse < 0;
     if (s->cfg.fuse < 0) s->cfg.fuse = MG_FUSE_AUTO;
+    if (fuse_by_default && cfg->dim == 3 && mg_grid_n(cfg->npts, 0) == 1023) s->cfg.fuse |= MG_FUSE_TRIPLE_NORM;
     if (s->cfg.pair_min_n <= 0) s->cfg.pair_min_n = (cfg->dim == 3) ? 255 : 2047;   /* where a two-sweep pass beats two sweeps
                                                                                       * (255^3: 0.107 ms against 2 x 0.063) */
     /* line smoothers: the passes that bake point Jacobi in are off (bits 1, 3, 5, 8-15); the fused residual + norm (0) and residual +
@@ -1113,8 +1117,10 @@ static int prolong_from(mg_solver *s, int P, int l) {
  * sweep is the first stage of the two-sweep pass that evaluates the norm (mgk_jacobi2_sumsq_mid_f64), whose second stage is the first
  * pre-smoothing sweep of the next cycle: 25 + 24 + 24 (two more pre-sweeps) + 18 (restriction) = 91 B per fine unknown and cycle.  The
  * iterate the norm belongs to is never stored: if the iteration stops, finalize_iterate() makes that one sweep. */
+static int triple_norm_ok(const mg_solver *s);
 static int pjp_ok(const mg_solver *s, int P) {
     const mg_level *L = &s->L[0];
+    if (P == 0 && triple_norm_ok(s)) return 0;       /* fuse bit 17: the post-smoothing is complete in every cycle, no sweep is owed */
     const int need = MG_FUSE_PROLONG_PAIR | MG_FUSE_SWEEP_RESTRICT | MG_FUSE_PAIRS | MG_FUSE_NORM_SWEEP | MG_FUSE_PROLONG_SWEEP | MG_FUSE_RESNORM;
     if ((s->cfg.fuse & need) != need || P != 0 || s->cfg.dim != 3 || s->cfg.mesh || s->cfg.ksp_type != MG_KSP_RICHARDSON) return 0;
     if (s->cfg.v[0] != 3 || s->levels < 2 || s->lgraph == 1 || L->n < s->cfg.pair_min_n || s->last_cycle) return 0;
@@ -1146,6 +1152,18 @@ static int prolong_triple_ok(const mg_solver *s, int P, int l) {
     if (s->lgraph && l >= s->lgraph - 1) return 0;
     return mg_triple_prolong_fits(s, l);
 }
+/* fuse bit 17 (MG_FUSE_TRIPLE_NORM; where bit 16 holds for both of its passes on level 0): post- and pre-smoothing of level 0 as two stacked
+ * passes (mg_triple.c) and the plain residual + restriction, (P + S1, S2, S3)(N + S1', S2', S3')(R) = 25 + 24 + 17 = 66 B per fine unknown and
+ * cycle.  prolong_smooth() takes the prolongation + three-sweep pass in every cycle (pjp_ok() yields: nothing is owed, u is the iterate the norm
+ * belongs to, finalize_iterate() has nothing to do); vcycle_once()'s norm pass makes all three pre-smoothing sweeps of the next cycle
+ * (spec_valid = 3), smooth() adopts them with one swap and sets no last_sweep_pending, and descend() restricts with the plain fused
+ * residual + restriction.  Level 0 swaps u / tmp TWICE per cycle (adoption, post-smoothing), three times in a cycle that has nothing to adopt
+ * (pair, sweep + restriction, post-smoothing); no recording holds its pointers: level 0 is outside the coarse-level graph and does not feed it */
+static int triple_norm_ok(const mg_solver *s) {
+    if (!(s->cfg.fuse & MG_FUSE_TRIPLE_NORM) || !mg_triple_norm_pass) return 0;
+    if (s->cfg.precision != MG_PREC_FP64 || s->cfg.pc_type != MG_PC_JACOBI) return 0;
+    return triple_mid_ok(s) && prolong_triple_ok(s, 0, 0);
+}
 static int finalize_iterate(mg_solver *s) {
     if (!s->iterate_behind) return 0;
     mg_level *L = &s->L[0];
@@ -1153,8 +1171,12 @@ static int finalize_iterate(mg_solver *s) {
     if (L->distributed) {
         CHK(ensure_u_ghosts(s, 0, L));
         CHK(mgk_jacobi_range_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u, (double *)F->tmp, 0, F->g.nz, NULL));
-    } else
-    CHK(mgk_jacobi_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u, (double *)F->tmp, NULL));
+    } else {
+        void *t = prof_begin(s, 0);                     /* a plain fine-level sweep like any other: profile kind 0 */
+        int rc2 = mgk_jacobi_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u, (double *)F->tmp, NULL);
+        prof_end(s, t);
+        CHK(rc2);
+    }
     swap_ptr(&F->u, &F->tmp);
     mgi_u_rewritten(F);
     s->iterate_behind = 0; s->spec_valid = 0;
@@ -1666,6 +1688,17 @@ static int vcycle_once(mg_solver *s) {
              * a cycle from the recording cycle's count, and the recorded restriction reads level 0's buffers) */
             const int two = (s->cfg.fuse & MG_FUSE_SWEEP_RESTRICT) && (s->cfg.fuse & MG_FUSE_PAIRS) && !L->distributed &&
                             s->cfg.v[0] >= 2 && L->n >= s->cfg.pair_min_n && s->lgraph != 1 && (s->cfg.dim == 2 || mgk_jacobi2_sumsq_ok_f64(&F->g));
+            if (triple_norm_ok(s)) {
+                /* fuse bit 17 (3-D, rows of 512 / 1024): ... and ALL THREE pre-smoothing sweeps of the next cycle in the stacked pass (mg_triple.c).
+                 * u is the complete iterate (nothing was owed) and stays untouched; smooth() adopts tmp with one swap and leaves no sweep to the
+                 * restriction.  Profile kind 2, as bit 16's three-sweep pass */
+                void *t = prof_begin_kind(s, 0, 2);
+                int rc2 = mg_triple_norm_pass(s, &ss);
+                prof_end(s, t);
+                CHK(rc2);
+                s->spec_valid = 3;
+                goto norm_done;
+            }
             if (j3_2d_ok(s, 0, 0, s->cfg.v[0])) {
                 /* 2-D: ... and ALL THREE pre-smoothing sweeps of the next cycle */
                 const int mesh = s->cfg.mesh != 0;
@@ -1828,6 +1861,8 @@ int mg_solver_num_levels(const mg_solver *s) { return s->levels; }
 void *mg_solver_debug_kernel_ctx(mg_solver *s) { return s ? (void *)s->ctx : NULL; }
 int mg_solver_tail_level(const mg_solver *s) { return s ? s->ltail : 0; }
 int mg_solver_prolong_triple_launches(const mg_solver *s, int l) { return (s && l >= 0 && l < s->levels) ? s->prolong_triple_launches[l] : 0; }
+int mg_solver_triple_norm_launches(const mg_solver *s) { return s ? s->triple_norm_launches : 0; }
+int mg_solver_graph_rerecorded(const mg_solver *s) { return s ? s->graph_rerecorded : 0; }
 int mg_solver_level_n(const mg_solver *s, int l) { return (l >= 0 && l < s->levels) ? s->L[l].n : -1; }
 int mg_solver_level_local_planes(const mg_solver *s, int l, int *z0) {
     if (l < 0 || l >= s->levels) return -1;

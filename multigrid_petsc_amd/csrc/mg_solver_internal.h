@@ -18,7 +18,7 @@
 /* y-line Jacobi: every pass that bakes POINT Jacobi into its kernel (bits 1, 3, 5, 8-15); the fused residual + norm and residual + restriction stay */
 #define MG_FUSE_POINT_JACOBI_PASSES (MG_FUSE_PROLONG_SWEEP | MG_FUSE_NORM_SWEEP | MG_FUSE_PAIRS | MG_FUSE_COARSE_ZERO_SWEEP | MG_FUSE_LDS_TAIL | \
                                      MG_FUSE_SWEEP_RESTRICT | MG_FUSE_ZERO_TRIPLE | MG_FUSE_PROLONG_PAIR | MG_FUSE_TRIPLE_2D | \
-                                     MG_FUSE_PROLONG_PAIR_SLAB | MG_FUSE_CHEBY | MG_FUSE_TRIPLE_MID)
+                                     MG_FUSE_PROLONG_PAIR_SLAB | MG_FUSE_CHEBY | MG_FUSE_TRIPLE_MID | MG_FUSE_TRIPLE_NORM)
 /* row-dependent coefficients (-mesh 1/2; 2-D, fp64): the two passes that exist in 3-D alone and have no row-table form */
 #define MG_FUSE_NO_ROW_TABLE_FORM   (MG_FUSE_MIXED_CORRECT | MG_FUSE_RES_RESTRICT_SMALL)
 
@@ -94,6 +94,7 @@ struct mg_solver {
     void *graph_u[2], *graph_tmp[2];   /* u / tmp of the level that feeds the recording, as the recorded kernels know them */
     int graph_rerecorded;   /* recordings thrown away because those pointers had changed (0 in every default configuration) */
     int prolong_triple_launches[MG_MAX_LEVELS];   /* launches of the prolongation + three-sweep pass per level since the solver was created (mg_triple.c) */
+    int triple_norm_launches;   /* launches of the norm + three-sweep pass of level 0 (fuse bit 17) since the solver was created (mg_triple.c) */
     /* profiling */
     int prof_on, prof_n;
     void *timers[MG_MAX_TIMERS];
@@ -159,6 +160,9 @@ extern int mg_triple_mid_pass(mg_solver *s, double *sumsq) __attribute__((weak))
  * sweeps in one pass (mgk_prolong_jacobi3_f64, named by mg_triple.c alone) instead of prolongation + sweep and a two-sweep pass */
 extern int mg_triple_prolong_fits(const mg_solver *s, int l) __attribute__((weak));   /* levels l, l + 1 have shapes the pass is built for */
 extern int mg_triple_prolong_pass(mg_solver *s, int l) __attribute__((weak));         /* level l: tmp = J(J(J(u + P u_{l+1}))); counts the launch */
+/* fuse bit 17 (MG_FUSE_TRIPLE_NORM): the norm of level 0's stored iterate and the three pre-smoothing sweeps of the next cycle in one stacked pass
+ * (mgk_jacobi3_sumsq_f64 on a shape mg_triple_mid_fits accepts), reached through a WEAK reference like the other two passes of mg_triple.c */
+extern int mg_triple_norm_pass(mg_solver *s, double *sumsq) __attribute__((weak));    /* level 0: tmp = J(J(J(u))), *sumsq = ||b - A u||^2; counts the launch */
 long mg_xline_stride(int n, int uniform);                                         /* row stride of the x table (mg_xline.c) */
 void mg_xline_factor(int n, int rows, const double *ctab, long gs, double *g);     /* the x table on the host (mg_xline.c) */
 

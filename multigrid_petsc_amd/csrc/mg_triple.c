@@ -29,6 +29,21 @@ int mg_triple_mid_pass(mg_solver *s, double *sumsq) {
     return 0;
 }
 
+/* fuse bit 17 (MG_FUSE_TRIPLE_NORM): tmp = J(J(J(u))) on level 0, *sumsq = || b - A u ||^2 of u itself -- the complete
+ * iterate the prolongation + three-sweep pass below left there -- so that the next cycle's pre-smoothing is this one pass:
+ *
+ *   (P + S1, S2, S3)  (N + S1', S2', S3')  (R)  =  25 + 24 + 17  =  66 B per fine unknown and cycle
+ *
+ * The stacked kernel with the norm of its input, four rows per wave (mgk_jacobi3_sumsq_f64 takes it on the shapes mg_triple_mid_fits accepts).
+ * u is not modified: a solve that stops here owes no sweep.  mg_solver.c times the launch (profile kind 2); counted here */
+int mg_triple_norm_pass(mg_solver *s, double *sumsq) {
+    mg_level *L = &s->L[0];
+    mg_fset *F = &L->f[0];
+    CHK(mgk_jacobi3_sumsq_f64(s->ctx, &F->g, L->coef, L->dinv, s->cfg.scale, (const double *)F->b, (const double *)F->u, (double *)F->tmp, sumsq, NULL));
+    s->triple_norm_launches++;
+    return 0;
+}
+
 /* The prolongation form of the same kernel: where the post-smoothing of a level runs through the generic branch of
  * prolong_smooth() -- level 1 of a 1025^3 solve in every cycle, level 0 in the last cycle of a call -- (P + S1)(S2, S3) = 25 + 24 B becomes
  * (P + S1, S2, S3) = 25 B per unknown of that level.  The level swaps u / tmp once instead of twice: mg_solver.c takes the pass only on

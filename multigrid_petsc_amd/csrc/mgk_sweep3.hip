@@ -758,6 +758,9 @@ __global__ void __launch_bounds__(64 * J3S_WAVES) k_jacobi3s(const typename std:
                 const unsigned long long mn = rown[q] & nm;
                 const double n0 = andm(r0, mn), n1 = andm(r1, Mx1 & mn);      // (lanes that store nothing: discarded at the end)
                 nacc += n0 * n0; nacc += n1 * n1;
+                // pins the accumulator in a register at this point (no instruction, no change of order): without it the scheduler hoists the
+                // 2 R residuals of the first stage over the rings and the input-norm form at R = 4 spills 19 registers
+                asm volatile("" : "+v"(nacc));
             }
         }
     };
@@ -891,7 +894,8 @@ __global__ void __launch_bounds__(64 * J3S_WAVES) k_jacobi3s(const typename std:
 static bool jacobi3s_shape_ok(const mgk_geom *g) { return g && g->dim == 3 && (g->nx + 1 == 512 || g->nx + 1 == 1024); }
 // which form the three-sweep entry points take: the stacked one where it is asked for by name (other shapes are then refused) and, unless the
 // knob names the independent-wave form or one of its variants, on the shapes it is built for -- it is the faster one there (1023^3: 5.60
-// against 7.27 ms, with the norm of the input 5.92 against 7.3; 511^3: 0.68 against 0.91; profiles/triple_mid/README.md)
+// against 7.27 ms; 511^3: 0.68 against 0.91; profiles/triple_mid/README.md.  With the norm of the input, four rows per wave as the other
+// forms: profiles/triple_norm/README.md; at three rows, MGK_TUNE_J3S_NORM_R3, it took 5.92 against 7.3 ms)
 static int jacobi3s_takes(const mgk_geom *g) {
     if (g_variant == MGK_TUNE_J3_3D_STACKED || g_variant == MGK_TUNE_J3_3D_STACKED_DISPATCH) return 1;
     if (g_variant == MGK_TUNE_J3_3D_WAVES || g_variant == MGK_TUNE_J3_3D_TY2 || g_variant == MGK_TUNE_J3_3D_TY3 || g_variant == MGK_TUNE_J3_3D_ROWWISE ||
@@ -899,7 +903,8 @@ static int jacobi3s_takes(const mgk_geom *g) {
     return jacobi3s_shape_ok(g) ? 1 : 0;
 }
 // PRO: the prolongation form, unew = J(J(J(u + P uc))) with uc on the coarse grid gc (g = 2 gc + 1 in every direction); no norm
-template <int NORM, bool PRO = false>
+// R: rows per wave, J3S_ROWS in every default form; 3 is the input-norm form of MGK_TUNE_J3S_NORM_R3
+template <int NORM, bool PRO = false, int R = J3S_ROWS>
 static int jacobi3s(mgk_ctx *c, const mgk_geom *g, const double *coef, double dinv, double scale, const double *b, const double *u, double *unew,
                     void *stream, int *norm_parts, const char *who, const mgk_geom *gc = nullptr, const double *uc = nullptr) {
     static_assert(!PRO || NORM == 0, "the prolongation form forms no norm");
@@ -916,9 +921,10 @@ static int jacobi3s(mgk_ctx *c, const mgk_geom *g, const double *coef, double di
         snprintf(msg, sizeof(msg), "%s: the stacked three-sweep pass is built for whole 3-D grids with rows of 512 or 1024 (nx = 511, 1023)", who);
         return fail(MGK_EINVAL, msg);
     }
-    // rows per wave: 4 (244-249 registers per lane, none in scratch); with the norm of the input 3: the first stage forms that norm while
-    // every ring is live, and the 4-row form would spill 19 registers to scratch
-    constexpr int R = (NORM == 1) ? 3 : J3S_ROWS, Y = J3S_WAVES * R - 6;
+    // rows per wave: 4 in every form (235-249 registers per lane, none in scratch, with the accumulator pin of stage(); the input-norm form
+    // spilled 19 registers without it and ran at 3 rows, which MGK_TUNE_J3S_NORM_R3 still selects: 18 of a block's 24 rows stored, not 26 of 32)
+    static_assert(R == J3S_ROWS || (R == 3 && NORM == 1 && !PRO), "the three-row form is built with the norm of the input alone");
+    constexpr int Y = J3S_WAVES * R - 6;
     typename std::conditional<PRO, J3spArgs, J3sArgs>::type a; memset(&a, 0, sizeof(a));
     if constexpr (PRO) {
         a.uc = uc + gc->org; a.nxc = gc->nx; a.nyc = gc->ny; a.nzc = gc->nz; a.crs = gc->pitch; a.cms = gc->plane;
@@ -983,8 +989,9 @@ extern "C" int mgk_jacobi3_sumsq_f64(mgk_ctx *c, const mgk_geom *g, const double
                                      const double *b, const double *u, double *unew, double *sumsq_host, void *stream) {
     if (!sumsq_host) return fail(MGK_EINVAL, "mgk_jacobi3_sumsq_f64: bad arguments");
     int nparts = 0;
-    int rc = jacobi3s_takes(g) ? jacobi3s<1>(c, g, coef, dinv, scale, b, u, unew, stream, &nparts, "mgk_jacobi3_sumsq_f64")
-                               : jacobi3_3d<true>(c, g, coef, dinv, scale, b, u, unew, stream, &nparts);
+    int rc = !jacobi3s_takes(g) ? jacobi3_3d<true>(c, g, coef, dinv, scale, b, u, unew, stream, &nparts)
+           : (g_variant == MGK_TUNE_J3S_NORM_R3) ? jacobi3s<1, false, 3>(c, g, coef, dinv, scale, b, u, unew, stream, &nparts, "mgk_jacobi3_sumsq_f64")
+                                                 : jacobi3s<1>(c, g, coef, dinv, scale, b, u, unew, stream, &nparts, "mgk_jacobi3_sumsq_f64");
     if (rc) return rc;
     return finish_to_host(c, nparts, 1, S(c, stream), sumsq_host);
 }

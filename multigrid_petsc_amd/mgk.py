@@ -59,6 +59,10 @@ class Tune(enum.IntEnum):
     NO_PROLONG_TRIPLE = 69
 
 
+# MGK_TUNE_J3S_NORM_R3 of include/mgk.h: the next value, beside the enum there and here (the enumerators mirror the C enum one to one)
+TUNE_J3S_NORM_R3 = 70
+
+
 @contextlib.contextmanager
 def tuning(variant=-1, zchunk=-1):
     """set the calling thread's tuning knobs for the body and put (-1, -1) back on the way out, exceptions included"""

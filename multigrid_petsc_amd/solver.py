@@ -27,7 +27,8 @@ class MgError(RuntimeError):
 
 class Fuse(enum.IntFlag):
     """The bits of Solver(fuse=...), mg_config.fuse: mg_fuse_bits of include/mgsolve.h, which says what each pass is.  The values are ABI
-    (plain ints are taken everywhere); value 64 is unassigned, accepted and ignored.  fuse=-1 selects FUSE_AUTO (below): DEFAULT and bit 16."""
+    (plain ints are taken everywhere); value 64 is unassigned, accepted and ignored.  fuse=-1 selects FUSE_AUTO (below): DEFAULT and bit 16 -- and bit 17
+    with them in 3-D at npts = 1025."""
     RESNORM = 1
     PROLONG_SWEEP = 2
     RES_RESTRICT = 4
@@ -50,6 +51,9 @@ class Fuse(enum.IntFlag):
 # MG_FUSE_TRIPLE_MID / MG_FUSE_AUTO of include/mgsolve.h: bit 16 stands beside the enum there and here (the enumerators mirror the C enum one to one)
 FUSE_TRIPLE_MID = 65536
 FUSE_AUTO = int(Fuse.DEFAULT) | FUSE_TRIPLE_MID
+# MG_FUSE_TRIPLE_NORM: bit 17, not part of FUSE_AUTO (fuse=-1 adds it in 3-D at npts = 1025, elsewhere it is opt-in): the 66-byte 3-D fine level,
+# post- and pre-smoothing of level 0 as two stacked passes
+FUSE_TRIPLE_NORM = 131072
 
 
 _KSP = {"richardson": 0, "chebyshev": 1}
@@ -90,6 +94,10 @@ def _lib():
     L.mg_solver_tail_level.argtypes = [vp]
     L.mg_solver_prolong_triple_launches.restype = i
     L.mg_solver_prolong_triple_launches.argtypes = [vp, i]
+    L.mg_solver_triple_norm_launches.restype = i
+    L.mg_solver_triple_norm_launches.argtypes = [vp]
+    L.mg_solver_graph_rerecorded.restype = i
+    L.mg_solver_graph_rerecorded.argtypes = [vp]
     L.mg_solver_level_n.restype = i
     L.mg_solver_level_n.argtypes = [vp, i]
     L.mg_solver_level_local_planes.restype = i
@@ -308,6 +316,16 @@ class Solver:
         """launches of the prolongation + three-sweep pass (fuse bit 16, mgk_prolong_jacobi3_f64) on level l since the solver was created"""
         return self.L.mg_solver_prolong_triple_launches(self.h, l)
 
+    @property
+    def triple_norm_launches(self):
+        """launches of the norm + three-sweep pass of level 0 (fuse bit 17, mgk_jacobi3_sumsq_f64) since the solver was created"""
+        return self.L.mg_solver_triple_norm_launches(self.h)
+
+    @property
+    def graph_rerecorded(self):
+        """recordings of the coarse-level graph thrown away because the pointers of the level that feeds it had changed (0 in every default configuration)"""
+        return self.L.mg_solver_graph_rerecorded(self.h)
+
     def level_n(self, l):
         return self.L.mg_solver_level_n(self.h, l)
 
@@ -331,7 +349,7 @@ class Solver:
 
     def profile_read(self, kind=0):
         """(total ms, launches) of the fine-level launches timed since profile(True): kind 0 plain sweeps,
-        kind 1 two-sweeps-in-one-pass launches, kind 2 the three-sweep pass of fuse bit 16"""
+        kind 1 two-sweeps-in-one-pass launches, kind 2 the three-sweep pass of fuse bit 16 and the norm + three-sweep pass of bit 17"""
         ms, n = C.c_double(), C.c_int()
         self._chk(self.L.mg_solver_profile_read_kind(self.h, kind, C.byref(ms), C.byref(n)))
         return ms.value, n.value

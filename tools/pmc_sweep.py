@@ -47,5 +47,8 @@ for _ in range(2):
     m._chk(L.mgk_jacobi3_sumsq_mid_f64(m.ctx, C.byref(g), coef, dinv, 6.0 / 7.0, b, u, out, C.byref(ss), None))
     # its prolongation form: prolongation + three sweeps in one pass (k_jacobi3s<.., PRO>)
     m._chk(L.mgk_prolong_jacobi3_f64(m.ctx, C.byref(g), C.byref(gc), coef, dinv, 6.0 / 7.0, b, uc, u, out, None))
+    # the norm pass of the 66-byte fine level: the stacked pass with the norm of its input (k_jacobi3s<4, 1>); the third pass of that level is the
+    # plain residual + restriction above
+    m._chk(L.mgk_jacobi3_sumsq_f64(m.ctx, C.byref(g), coef, dinv, 6.0 / 7.0, b, u, out, C.byref(ss), None))
 m.sync()
 m.close()
