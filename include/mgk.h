@@ -754,6 +754,9 @@ enum mgk_tune {
  * form with the norm of the input at THREE rows per wave (k_jacobi3s<3, 1>: 18 of a block's 24 rows stored) instead of four (26 of 32) -- the
  * form before the accumulator pin, kept as the A/B switch of one build */
 #define MGK_TUNE_J3S_NORM_R3 70
+/* jacobi3_3d, jacobi3_sumsq, jacobi3_sumsq_mid, prolong_jacobi3 on rows of 512 / 1024: the stacked form loads b NON-TEMPORALLY, as it did
+ * until plain loads measured faster (the same field and the same sums, bit for bit): the A/B switch of one build */
+#define MGK_TUNE_J3S_B_NT 71
 
 /* tuning knobs (profiling only), per calling thread: <=0 keeps the built-in choice.  They are GLOBAL to that thread, not per kernel -- set
  * them back to (-1, -1) after measuring one kernel.  The second argument, > 0, is the length of a chunk of the marching axis (planes, rows

@@ -15,7 +15,7 @@ int  mgk_jacobi3_mid_ok_f64(const mgk_geom *g);
 /* unew = J(J(J(u))) and *sumsq_host = || b - A J(u) ||^2, the residual of the FIRST sweep's output (which is not stored), in one pass of
  * 24 B per unknown: the three-sweep counterpart of mgk_jacobi2_sumsq_mid_f64.  Bit-identical to three mgk_jacobi_f64 calls; the sum is formed
  * from per-block partials in a fixed order.  Other shapes: MGK_EINVAL with a message.  The knobs of mgk_set_tuning: the chunk length in z,
- * MGK_TUNE_J3_3D_STACKED_DISPATCH (tiles in dispatch order), MGK_TUNE_NO_EXACT_FMA. */
+ * MGK_TUNE_J3_3D_STACKED_DISPATCH (tiles in dispatch order), MGK_TUNE_J3S_B_NT (b loaded non-temporally), MGK_TUNE_NO_EXACT_FMA. */
 int  mgk_jacobi3_sumsq_mid_f64(mgk_ctx *ctx, const mgk_geom *g, const double *coef, double dinv, double scale,
                                const double *b, const double *u, double *unew, double *sumsq_host, void *stream);
 
@@ -25,7 +25,7 @@ int  mgk_prolong_jacobi3_ok_f64(const mgk_geom *gf, const mgk_geom *gc);
 /* unew = J(J(J(u + P uc))): the prolongation, its correction and three post-smoothing sweeps in one pass of 25 B per fine unknown (u, b and
  * uc / 8 read, unew written once).  Bit-identical to mgk_prolong_jacobi_f64 followed by two mgk_jacobi_f64.  unew must not be u, b or uc;
  * u, b and uc are not modified.  Other shapes: MGK_EINVAL with a message.  Knobs: the chunk length in z, MGK_TUNE_J3_3D_STACKED_DISPATCH,
- * MGK_TUNE_NO_EXACT_FMA. */
+ * MGK_TUNE_J3S_B_NT, MGK_TUNE_NO_EXACT_FMA. */
 int  mgk_prolong_jacobi3_f64(mgk_ctx *ctx, const mgk_geom *gf, const mgk_geom *gc, const double *coef, double dinv, double scale,
                              const double *b, const double *uc, const double *u, double *unew, void *stream);
 

@@ -14,4 +14,4 @@ built libraries or without a HIP device raises.
 """
 from ._lib import load_mgk, load_mgpetsc, LibraryMissing  # noqa: F401
 from .solver import Fuse, FUSE_AUTO, FUSE_TRIPLE_MID, FUSE_TRIPLE_NORM  # noqa: F401
-from .mgk import Tune, TUNE_J3S_NORM_R3, tuning  # noqa: F401
+from .mgk import Tune, TUNE_J3S_B_NT, TUNE_J3S_NORM_R3, tuning  # noqa: F401

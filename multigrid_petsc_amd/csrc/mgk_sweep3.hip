@@ -660,7 +660,8 @@ struct J3spArgs : J3sArgs {
 // coarse plane is due every second step: plane (t + 4) / 2 is requested at the top of an EVEN step t (global parity: a chunk may start at
 // any z), stored into its slot before the barrier that ends the step and first read in step t + 1.  Coarse indices are clamped into the
 // ghost ring -1 .. nc: what a clamped index reads lands on positions the masks clear.
-template <int R, int NORM, bool EX, bool PRO = false>
+// BNT: b is loaded non-temporally (the policy until DESIGN.md section 4 (xxiii), MGK_TUNE_J3S_B_NT); by default with plain loads, as u is
+template <int R, int NORM, bool EX, bool PRO = false, bool BNT = false>
 __global__ void __launch_bounds__(64 * J3S_WAVES) k_jacobi3s(const typename std::conditional<PRO, J3spArgs, J3sArgs>::type a) {
     constexpr int NW = J3S_WAVES, Y = NW * R - 6;
     constexpr unsigned XROW = 1024, XBUF = 3 * NW * 2 * XROW;   // a deposited row: 64 lanes x 16 B; a buffer: 3 fields x NW waves x 2 rows
@@ -725,7 +726,10 @@ __global__ void __launch_bounds__(64 * J3S_WAVES) k_jacobi3s(const typename std:
     auto ldb = [&](VT (&P)[R], int z) {
         const char *pz = bb_ + 8 * (long)min(max(z, 0), a.nz - 1) * a.ms;
 #pragma unroll
-        for (int q = 0; q < R; q++) P[q] = ldv_stream(reinterpret_cast<const double *>(pz + bro[q] + (size_t)lo), true);
+        for (int q = 0; q < R; q++) {
+            if constexpr (BNT) P[q] = ldv_stream(reinterpret_cast<const double *>(pz + bro[q] + (size_t)lo), true);
+            else P[q] = *reinterpret_cast<const VT *>(pz + bro[q] + (size_t)lo);
+        }
     };
     // one sweep of the wave's R rows, term by term over the rows (the per-point expression and order of k_jacobi3_3d: 2 R independent sums).
     // hs / hn: the rows below the first and above the last row of the centre plane.  zm: all ones if the plane is inside the grid;
@@ -954,8 +958,22 @@ static int jacobi3s(mgk_ctx *c, const mgk_geom *g, const double *coef, double di
         a.partials = c->partials;
         *norm_parts = (int)nblk;
     }
-    if (exact_fma7(coef)) hipLaunchKernelGGL((k_jacobi3s<R, NORM, true, PRO>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
-    else hipLaunchKernelGGL((k_jacobi3s<R, NORM, false, PRO>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
+    // b: plain loads.  A block's rows 0-5 and 26-31 of b, as of u, are rows the blocks below and above load too, and a non-temporal load left
+    // none of them in L2 for the neighbour: at 1023^3 the norm pass read 21.1 B per unknown with them and 19.4 B without, 5.63 against 5.11 ms
+    // (profiles/stacked_l2/README.md).  MGK_TUNE_J3S_B_NT restores the non-temporal loads; the three-row form
+    // keeps them (it is itself an earlier form, MGK_TUNE_J3S_NORM_R3)
+    const bool bnt = (R != J3S_ROWS) || g_variant == MGK_TUNE_J3S_B_NT;
+    const bool ex = exact_fma7(coef);
+    if constexpr (R == J3S_ROWS) {
+        if (!bnt) {
+            if (ex) hipLaunchKernelGGL((k_jacobi3s<R, NORM, true, PRO, false>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
+            else hipLaunchKernelGGL((k_jacobi3s<R, NORM, false, PRO, false>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
+        }
+    }
+    if (bnt) {
+        if (ex) hipLaunchKernelGGL((k_jacobi3s<R, NORM, true, PRO, true>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
+        else hipLaunchKernelGGL((k_jacobi3s<R, NORM, false, PRO, true>), dim3(nblk), dim3(64 * J3S_WAVES), 0, S(c, stream), a);
+    }
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -61,6 +61,8 @@ class Tune(enum.IntEnum):
 
 # MGK_TUNE_J3S_NORM_R3 of include/mgk.h: the next value, beside the enum there and here (the enumerators mirror the C enum one to one)
 TUNE_J3S_NORM_R3 = 70
+# MGK_TUNE_J3S_B_NT: the stacked 3-D three-sweep pass loads b non-temporally, as it did before plain loads became its default
+TUNE_J3S_B_NT = 71
 
 
 @contextlib.contextmanager
